@@ -23,6 +23,15 @@ inside the timed step (north_star: collective only for solution collection).
 `--gpus N` without torchrun's RANK in the environment starts N ranks itself
 (torch.distributed.run as a child process, before this process touches the
 GPU) and fails if fewer than N GPUs are visible.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line: the rate, the
+roofline and the statistics of those steps.  `--full` adds the legs that take runs of
+their own after the timed region: the host-buffer API's PCIe-inclusive rate, the CPU
+baseline (C oracle) with the bit-exact parity of the GPU results against it, the golden
+fixtures through the GPU host API and C4's lone-game critical path.
+`--dump-outputs DIR` writes the results of the last timed step, as a caller of the
+timed path receives them, to DIR/<field>.npy (float64) for output-for-output
+comparison of two builds: θ depends only on the arguments.
 """
 
 from __future__ import annotations
@@ -49,6 +58,7 @@ PROFILE_DIR = os.environ.get("MCPX_PROFILE_DIR") or os.path.join(ROOT, "profiles
 DEFAULT_GLOBAL = {"c3": 65536, "c5": 4096, "c4": 1024}
 QP_FIELDS = ("x", "y", "s", "kkt_error", "eps", "outer_iters", "status", "newton_iters")
 C4_FIELDS = QP_FIELDS
+DUMP_BUDGET = 64 * 2 ** 20  # bytes --dump-outputs may write
 
 
 def lu_flops(N: int) -> float:
@@ -174,6 +184,33 @@ def fixture_parity() -> dict:
     return {"files": len(files), "instances": inst, "failed_files": bad, "pass": not bad and bool(files)}
 
 
+def dump_outputs(dirname: str, out: dict, m: int) -> None:
+    """`--dump-outputs`: every per-instance result array of `out` (torch tensors, instance-major;
+    None entries skipped) as `dirname`/<field>.npy in float64.  `active_mask` is written as its
+    first m bits, one 0/1 column per inequality (a uint64 word does not fit a float64).  At most
+    DUMP_BUDGET bytes in all: a larger batch is cut to a fixed sample of instances (numpy PCG64
+    seeded 0, the same rows of every field, ascending; their indices in sample_rows.npy)."""
+    arrays = {}
+    for k, t in out.items():
+        if t is None:
+            continue
+        v = t.detach().cpu().numpy()
+        if k == "active_mask":
+            j = np.arange(m)
+            v = (v.view(np.uint64)[:, j // 64] >> (j % 64).astype(np.uint64)) & np.uint64(1)
+        arrays[k] = np.ascontiguousarray(v, dtype=np.float64)
+    B = next(iter(arrays.values())).shape[0]
+    assert all(v.shape[0] == B for v in arrays.values()), "dumped fields differ in their instance count"
+    row_bytes = 8 + sum(v[:1].nbytes for v in arrays.values())  # one instance of every field + its index
+    if B * row_bytes > DUMP_BUDGET:
+        rows = np.sort(np.random.default_rng(0).choice(B, DUMP_BUDGET // row_bytes, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+
+
 def host_cpus() -> dict:
     """CPUs this process can actually use: its affinity set, capped by the cgroup CPU
     quota (a GPU box grants 16 of the machine's 256 hardware threads; GNU `nproc`
@@ -204,6 +241,14 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the host-buffer "
+                         "API's rate (--host-runs), the CPU baseline with oracle parity (--cpu-sample), the golden "
+                         "fixtures through the GPU and --lane-change's lone-game critical path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the arrays a caller of the timed path "
+                         "receives) to DIR/<field>.npy, float64, at most 64 MB (a fixed seeded sample of "
+                         "instances beyond that)")
     ap.add_argument("--global-batch", type=int, default=0,
                     help="instances over all GPUs, sharded (strong scaling); 0 = the BASELINE config's")
     ap.add_argument("--batch", type=int, default=0, help="instances per GPU (weak scaling) instead")
@@ -217,9 +262,9 @@ def parse(argv=None):
                     help="affine: the same QPs handed over as affine-family data (P = M, Q = -A^T, R = A, S = 0, "
                          "g = -phi, h = -b), the layout the Julia shim's affine_parameters produces (INTEGRATION.md)")
     ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="instances in the CPU-baseline sample (-1 = 2048 per thread, 0 = skip)")
+                    help="with --full: instances in the CPU-baseline sample (-1 = 2048 per thread, 0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every CPU this process may use (nproc)")
-    ap.add_argument("--host-runs", type=int, default=5, help="timed runs of the host-buffer API (median)")
+    ap.add_argument("--host-runs", type=int, default=5, help="with --full: timed runs of the host-buffer API (median)")
     ap.add_argument("--sens", action="store_true",
                     help="BASELINE C5: each step is the batched solve + the rrule pullback (VJP kernel) of "
                          "f = Σx² + Σy² (src/AutoDiff.jl:42-82, test/runtests.jl:72-75)")
@@ -499,6 +544,8 @@ def main_lane_change(a, world, rank, local, dist, pl):
                                                                   [newton, solved])
     if rank != 0:
         return
+    if a.dump_outputs:  # rank 0's games: the shards are not collected in this mode
+        dump_outputs(a.dump_outputs, dict(out, **({"dtheta": dth, "vjp_status": vst} if a.sens else {})), m)
     # the generated module's content hash (its kernel headers included) keys the evidence too:
     # the nonlinear kernels live in the module, not in libmcpx.so
     cfg = {"mode": "c4s" if a.sens else "c4", "horizon": a.lane_change, "batch_per_gpu": B, "linear_solver": ls,
@@ -519,28 +566,30 @@ def main_lane_change(a, world, rank, local, dist, pl):
                   "); bound: per-wave latency (PMC: waves stall on LDS/VALU dependencies, DESIGN.md §4)",
                   structural=True)
     rl["frac_structural"] = rl["executed_frac"]
-    # critical path: the game with the most Newton steps solved alone (one wave on an idle GPU,
-    # the same kernel): its time over the launch's says how much of the launch is that one
-    # game's chain of dependent steps (≈ 1: tail-bound, the rest of the batch fits beside it)
-    imax = int(torch.argmax(out["newton_iters"]).item())
-    nmax = int(out["newton_iters"][imax].item())
-    one = alloc_device_outputs(1, n, m, dev)
-    th1 = theta[imax:imax + 1].contiguous()
-    lone = []
-    for rep in range(3):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        solve_batch_device(_abi.FAMILY_NONLINEAR, n, m, th1, one, tol=a.tol, linear_solver=ls, stream=stream,
-                           module=module, kernel=a.kernel)
-        e1.record(stream)
-        torch.cuda.synchronize(dev)
-        if rep:
-            lone.append(e0.elapsed_time(e1))
-    lone_ms = float(np.mean(lone))
-    rl["critical_path"] = {"longest_game_newton": nmax, "lone_game_ms": lone_ms,
-                           "lone_step_us": lone_ms * 1e3 / max(nmax, 1), "frac_of_launch": lone_ms / kern_ms,
-                           "note": "the longest game of rank 0's batch solved alone (B = 1, same kernel) over the "
-                                   "batch launch's kernel time: the share of the launch its dependent chain sets"}
+    if a.full:
+        # critical path: the game with the most Newton steps solved alone (one wave on an idle GPU,
+        # the same kernel): its time over the launch's says how much of the launch is that one
+        # game's chain of dependent steps (≈ 1: tail-bound, the rest of the batch fits beside it)
+        imax = int(torch.argmax(out["newton_iters"]).item())
+        nmax = int(out["newton_iters"][imax].item())
+        one = alloc_device_outputs(1, n, m, dev)
+        th1 = theta[imax:imax + 1].contiguous()
+        lone = []
+        for rep in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            solve_batch_device(_abi.FAMILY_NONLINEAR, n, m, th1, one, tol=a.tol, linear_solver=ls, stream=stream,
+                               module=module, kernel=a.kernel)
+            e1.record(stream)
+            torch.cuda.synchronize(dev)
+            if rep:
+                lone.append(e0.elapsed_time(e1))
+        lone_ms = float(np.mean(lone))
+        rl["critical_path"] = {"longest_game_newton": nmax, "lone_game_ms": lone_ms,
+                               "lone_step_us": lone_ms * 1e3 / max(nmax, 1), "frac_of_launch": lone_ms / kern_ms,
+                               "note": "the longest game of rank 0's batch solved alone (B = 1, same kernel) over "
+                                       "the batch launch's kernel time: the share of the launch its dependent "
+                                       "chain sets"}
     res = {
         "metric": ("MCP solve+VJP/sec (lane-change trajectory game, generated nonlinear module, rrule pullback of "
                    "x₁ as examples/utils.jl:236-261)" if a.sens else
@@ -564,7 +613,7 @@ def main_lane_change(a, world, rank, local, dist, pl):
         res["vjp_kernel_ms"] = vjp_ms
         res["vjp_kernel"] = "mcpx_nl_vjp_wg"
         res["vjp_status_nonzero"] = int((vst != 0).sum().item())
-    if world == 1 and a.cpu_sample != 0:
+    if a.full and world == 1 and a.cpu_sample != 0:
         from oracle import coracle
 
         coracle.build()
@@ -655,11 +704,18 @@ def main_qp(a, world, rank, local, dist, pl, distributed):
     kern_ms = float(np.mean(ms[0]))
     vjp_ms = float(np.mean(ms[1])) if (a.sens and not fused) else 0.0
     step_s = [sum(t) * 1e-3 for t in zip(*ms)]  # per-step device time of the solve (+ pullback)
+    if a.dump_outputs and rank == 0:
+        # what a caller holds after the step: the gathered global batch with N ranks, else this rank's
+        got = gather.unpack([shard_range(pl["global_batch"], world, r)[1] for r in range(world)]
+                            if pl["scaling"] == "strong" else None) if distributed else dict(out)
+        if a.sens and not distributed:
+            got.update(dtheta=dtheta, vjp_status=vstat)
+        dump_outputs(a.dump_outputs, got, m)
     # PCIe-inclusive rate of the host-buffer API (mcpx_solve_batch: H→D θ, solve, D→H
     # results), median of --host-runs runs after one warm-up;
     # reported beside `value`, never as it
     host = None
-    if world == 1 and a.host_runs > 0 and not a.sens:
+    if a.full and world == 1 and a.host_runs > 0 and not a.sens:
         from mcp_amd.batch import alloc_host_outputs, pinned
 
         def host_runs(out=None):
@@ -780,7 +836,7 @@ def main_qp(a, world, rank, local, dist, pl, distributed):
                                      "executed: the LU of the slack-eliminated (n+m)-dim system the kernel "
                                      "factors; bytes = θ read + ∂θ written + z and cotangents"},
         }
-    if world == 1 and a.cpu_sample != 0:
+    if a.full and world == 1 and a.cpu_sample != 0:
         from oracle import coracle
 
         coracle.build()
@@ -802,7 +858,7 @@ def main_qp(a, world, rank, local, dist, pl, distributed):
                                                  {"dtheta": rd, "status": rs}, ("dtheta", "status"), kv,
                                                  "oracle_vjp_batch on the GPU's solutions")
         res["cpu_baseline"] = cb
-    if world == 1 and not a.sens and not fam:
+    if a.full and world == 1 and not a.sens and not fam:
         res["parity_fixtures"] = fixture_parity()
     print(json.dumps(res), flush=True)
 

@@ -167,15 +167,80 @@ def test_cli_has_every_baseline_mode():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True,
                          text=True, check=True).stdout
     for flag in ("--gpus", "--steps", "--warmup", "--sens", "--lane-change", "--gather", "--cpu-sample",
-                 "--global-batch", "--batch", "--host-runs"):
+                 "--global-batch", "--batch", "--host-runs", "--full", "--dump-outputs"):
         assert flag in out
+
+
+def test_plain_run_is_the_default():
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_layout_and_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 .npy per result field, None fields skipped, the active mask as
+    one 0/1 column per inequality; beyond the byte budget the same fixed sample of instances of
+    every field, identical from call to call."""
+    import torch
+
+    B, n, m = 10, 3, 66
+    mask = torch.zeros(B, 2, dtype=torch.int64)
+    mask[1, 0] = -(1 << 63)  # bit 63 of word 0
+    mask[2, 1] = 2           # inequality 65
+    out = {"x": torch.arange(B * n, dtype=torch.float64).view(B, n), "status": torch.arange(B, dtype=torch.int32),
+           "fail_reason": torch.arange(B, dtype=torch.uint8), "active_mask": mask, "alpha_trace": None}
+    bench.dump_outputs(str(tmp_path / "a"), out, m)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["active_mask", "fail_reason", "status", "x"]
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["x"].shape == (B, n) and got["status"].shape == (B,) and got["active_mask"].shape == (B, m)
+    assert np.array_equal(got["x"], out["x"].numpy()) and np.array_equal(got["status"], np.arange(B))
+    want = np.zeros((B, m))
+    want[1, 63] = want[2, 65] = 1.0
+    assert np.array_equal(got["active_mask"], want)
+    # a budget of 4 instances: (index + x + status + fail_reason + mask columns) × 8 bytes each
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4 * 8 * (1 + n + 1 + 1 + m) + 7)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), out, m)
+    b = {f[:-4]: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    rows = b["sample_rows"].astype(int)
+    assert len(rows) == 4 and len(set(rows)) == 4 and list(rows) == sorted(rows)
+    assert np.array_equal(b["x"], got["x"][rows]) and np.array_equal(b["status"], rows)
+    assert sum(v.nbytes for v in b.values()) <= bench.DUMP_BUDGET
+    for f in os.listdir(tmp_path / "b"):
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+
+
+@pytest.mark.gpu
+def test_gpu_bench_plain_line_and_dump(tmp_path, oracle_lib):
+    """A plain run: the headline fields, none of the --full legs, and --dump-outputs holding the
+    last step's results — bit-identical to the C oracle's on the same seeded θ."""
+    from mcp_amd.qp_benchmark import generate_global_slice
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--global-batch", "300",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True,
+                       text=True, timeout=110, check=True)
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["metric"] == bench.METRIC and d["unit"] == "solves/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["steps"] == 3 and d["summary_statistics"]["ip"]["steps"] == 3
+    assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(300 / (d["ms_per_step"] * 1e-3))
+    assert d["host_api"] is None and not {"cpu_baseline", "parity", "parity_fixtures"} & set(d)
+    ref = oracle_lib.solve_batch(0, 32, 16, generate_global_slice(1, 32, 16, 0.0, 0, 300), tol=1e-6,
+                                 linear_solver="schur")
+    for k in bench.QP_FIELDS + ("fail_reason",):
+        got = np.load(tmp_path / (k + ".npy"))
+        assert got.dtype == np.float64 and got.shape == ref[k].shape
+        assert np.array_equal(got, ref[k].astype(np.float64), equal_nan=True), k
+    am = np.load(tmp_path / "active_mask.npy")
+    assert am.shape == (300, 16) and np.array_equal(am, (ref["active_mask"][:, :1] >> np.arange(16, dtype=np.uint64)) & 1)
 
 
 @pytest.mark.gpu
 def test_gpu_bench_lane_change_line():
     """The C4 bench line on a small batch: one JSON line, statuses equal to the C oracle's."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--lane-change", "2", "--global-batch",
-                        "64", "--steps", "1", "--warmup", "1", "--cpu-sample", "64"], capture_output=True,
+                        "64", "--steps", "1", "--warmup", "1", "--full", "--cpu-sample", "64"], capture_output=True,
                        text=True, timeout=110, check=True)
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert d["config"]["kkt_dim"] == 140 and d["n_gpus"] == 1
@@ -187,7 +252,7 @@ def test_gpu_bench_lane_change_line():
 def test_gpu_bench_c3_small_line():
     """The C3 line on a small global batch, with the host-API median and the CPU legs."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--global-batch", "2048", "--steps", "2",
-                        "--warmup", "1", "--cpu-sample", "256", "--host-runs", "2"], capture_output=True,
+                        "--warmup", "1", "--full", "--cpu-sample", "256", "--host-runs", "2"], capture_output=True,
                        text=True, timeout=110, check=True)
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert d["scaling"] == "strong" and d["config"]["global_batch"] == 2048

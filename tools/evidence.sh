@@ -19,5 +19,6 @@ export TMPDIR=/tmp
 bash tools/gpu_profile.sh "$NAME" "${ARGS[@]}" || exit $?
 python tools/prof_summary.py gpurun_out/prof_$NAME --dst $DST > gpurun_out/prof_$NAME/summary.log 2>&1 || { tail -5 gpurun_out/prof_$NAME/summary.log; exit 8; }
 KEY=$(python -c "import json; print(json.loads(open('gpurun_out/prof_$NAME/bench.json').read().strip().splitlines()[-1])['evidence']['key'])") || exit 8
-MCPX_PROFILE_DIR=$DST timeout -k 10 400 python bench.py "${ARGS[@]}" > $DST/bench_$KEY.json 2> gpurun_out/prof_$NAME/final.err || { tail -5 gpurun_out/prof_$NAME/final.err; exit 9; }
+# --full: the committed line carries the host-API rate, the CPU baseline and the oracle parity too
+MCPX_PROFILE_DIR=$DST timeout -k 10 400 python bench.py "${ARGS[@]}" --full > $DST/bench_$KEY.json 2> $DST/bench_$KEY.err || { tail -5 $DST/bench_$KEY.err; exit 9; }
 cut -c1-240 $DST/bench_$KEY.json
