@@ -346,9 +346,15 @@ int mcpx_jvp_batch_device(const mcpx_desc* desc, const double* theta, const doub
  * (e.g. the lane change at T = 10: n = 200, m = 250, KKT dimension 700), and
  * the one-wave band SCHUR kernel when the reordered Schur complement has a
  * narrow band (MCPX_KERNEL_BAND); another linear_solver is MCPX_EUNSUPPORTED.
+ * The sensitivity kernels reach further than the workgroup solve kernels: their
+ * blocked LU keeps a panel of 16, 8 or 4 columns in LDS, the widest that fits
+ * (the lane change at T = 30, n = 600, m = 750: 8 columns for the pullback's
+ * 1350 rows, 4 for the tangents' 2100).  The width changes no bit of a result.
  */
 typedef struct mcpx_module mcpx_module;
-/* Sensitivity kernels of a module (bits of the mcpx_module_dims kernel mask) */
+/* Sensitivity kernels of a module (bits of the mcpx_module_dims kernel mask): set when a
+ * panel of at least 4 columns of the factored system (VJP: n + m rows; JVP and the condition
+ * estimate: n + 2m rows) fits the LDS, 24·(n+2m) + rows·(8·width + 7) + 512 <= 161792 bytes */
 #define MCPX_MODULE_VJP 6
 #define MCPX_MODULE_JVP 7
 #define MCPX_MODULE_SCHUR_MW 8  /* the 4-wave SCHUR solve kernel (MCPX_KERNEL_MULTIWAVE) */
@@ -378,8 +384,10 @@ int mcpx_solve_batch_module_device(mcpx_module* mod, const mcpx_desc* desc, cons
  * trajectory games of src/game.jl.  Same argument meaning as mcpx_vjp_batch /
  * mcpx_jvp_batch with p = the module's θ dimension; one workgroup per instance
  * (VJP: the (n+m)-dim reduced ∇F_zᵀ system, JVP: the (n+2m)-dim ∇F_z, blocked LU
- * with partial pivoting).  MCPX_EUNSUPPORTED when the module has no such kernel
- * (mask bits MCPX_MODULE_VJP / MCPX_MODULE_JVP). */
+ * with partial pivoting, panel of 16 / 8 / 4 columns by what fits the LDS).  A call takes
+ * at most 4 GiB of workspace: systems whose slot is tens of MB run on fewer workgroups.
+ * MCPX_EUNSUPPORTED when the module has no such kernel (mask bits MCPX_MODULE_VJP /
+ * MCPX_MODULE_JVP: not even 4 columns fit). */
 int mcpx_vjp_batch_module(mcpx_module* mod, const mcpx_desc* desc, const double* theta, const double* x,
                           const double* y, const double* s, const double* gx, const double* gy,
                           const double* gs, int num_devices, double* dtheta, int32_t* status);

@@ -398,6 +398,12 @@ class PrimalDualMCP:
 
             self.family = _abi.FAMILY_NONLINEAR
             self.nl = codegen.NLSystem(G, H, xs, ys, ts)
+            # backend_options={"sens_panel_max": 8 | 4}: cap the panel width of the module's
+            # sensitivity kernels (NLSystem.sens_panels; same bits, a code object of its own)
+            cap = (backend_options or {}).get("sens_panel_max", 16)
+            if cap not in (16, 8, 4):
+                raise ValueError(f"backend_options['sens_panel_max'] must be 16, 8 or 4, not {cap!r}")
+            self.nl.sens_panel_max = cap
             self.theta_map = ThetaMap(list(ts), ts)  # θ' = θ
             return
         P = [[CG[i][j] for j in range(n)] for i in range(n)]

@@ -274,6 +274,27 @@ class NLSystem:
             "dense": n + 2 * m >= 1 and lds(n + 2 * m) <= WG_LDS_LIMIT,
         }
 
+    # widest panel of the sensitivity kernels' blocked LU (backend_options "sens_panel_max"):
+    # MCPX_NL_SENS_NB_MAX of csrc/ipm_nl_kernel.hpp.  Part of module_key(), not of the generated text.
+    sens_panel_max = 16
+
+    def sens_panels(self) -> dict:
+        """Panel width of the module's sensitivity kernels (MCPX_NL_SENS_NB_VJP / _JVP of
+        csrc/ipm_nl_kernel.hpp): the widest of 16 / 8 / 4, at most sens_panel_max, whose LDS
+        3·8·(n+2m) + NS·(8·NB + 7) + 512 fits; 0 = the module has no such kernel.  The pullback
+        factors NS = n + m rows, tangents and the condition estimate NS = n + 2m.  The width
+        changes no bit of the result."""
+        n, m = self.n, self.m
+
+        def width(ns):
+            for nb in (16, 8, 4):
+                lds = 8 * 3 * (n + 2 * m) + ns * (8 * nb + 7) + 512
+                if ns >= 1 and nb <= self.sens_panel_max and lds <= WG_LDS_LIMIT:
+                    return nb
+            return 0
+
+        return {"vjp": width(n + m), "jvp": width(n + 2 * m)}
+
     def default_solver(self) -> str:
         """The cheapest elimination a kernel exists for: SCHUR, then REDUCED, then
         DENSE; the one-wave kernels when the system fits them, else the
@@ -569,6 +590,7 @@ class NLSystem:
             "// small ones let the compiler batch the loads.",
             "#define MCPX_NL_Z(j) (((const " + ("volatile " if self.n + self.m > Z_VOLATILE_ABOVE else "")
             + "__attribute__((address_space(3))) double*)z)[j])",
+            *([f"#define MCPX_NL_SENS_NB_MAX {self.sens_panel_max}"] if self.sens_panel_max != 16 else []),
             self.body,
             '#include "ipm_nl_kernel.hpp"',
             "",
@@ -580,6 +602,8 @@ class NLSystem:
         oracle's cache key, covers the generated text only)."""
         h = hashlib.sha256(self.key.encode())
         h.update(deps_hash().encode())
+        if self.sens_panel_max != 16:  # a code object of its own (the oracle's self.key is unaffected)
+            h.update(f"sens_panel_max={self.sens_panel_max}".encode())
         return h.hexdigest()[:24]
 
     def module_path(self) -> str:
@@ -608,6 +632,18 @@ class NLSystem:
             f.write(deps_hash())
         shutil.rmtree(tmp_dir, ignore_errors=True)
         return path
+
+
+def build_modules(systems, verbose: bool = False) -> list:
+    """build_module() of every NLSystem of `systems`, the hipcc runs side by side (MAX_JOBS, else
+    the CPUs, at most 16).  `systems` may be a generator: each compile starts as soon as its
+    system is traced, while the next one is traced.  Returns the paths in order."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    jobs = int(os.environ.get("MAX_JOBS", "0")) or min(16, os.cpu_count() or 1)
+    with ThreadPoolExecutor(max_workers=max(1, jobs)) as pool:
+        futures = [pool.submit(nl.build_module, verbose) for nl in systems]
+        return [f.result() for f in futures]
 
 
 def deps_hash() -> str:

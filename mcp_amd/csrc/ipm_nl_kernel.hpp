@@ -995,6 +995,23 @@ __device__ __forceinline__ void solve(const KernelArgs& args) {
 #define MCPX_NL_CAN_WG_DENSE (MCPX_NL_NV >= 1 && MCPX_NL_WG_LDS(MCPX_NL_NV) <= MCPX_NL_WG_LIMIT)
 #define MCPX_NL_CAN_WG_SCHUR (!MCPX_NL_HAS_S && MCPX_NL_N >= 1 && MCPX_NL_WG_LDS(MCPX_NL_N) <= MCPX_NL_WG_LIMIT)
 
+// ---- sensitivity kernels (sens_wg_impl.hpp): the panel width of their blocked LU ----
+// LDS of sens_instances<…, NV, NS, …, NB>: as above with a panel of NB columns.  The width
+// is the widest of 16 / 8 / 4 (at most MCPX_NL_SENS_NB_MAX: backend_options "sens_panel_max",
+// which lets a small module run the narrow panels) that fits; 0: not even 4 columns fit and
+// the module has no such kernel.  The pullback factors NS = n + m rows, tangents and the
+// condition estimate NS = n + 2m.  Every width gives the same bits (wg::LuShared).
+#ifndef MCPX_NL_SENS_NB_MAX
+#define MCPX_NL_SENS_NB_MAX 16
+#endif
+#define MCPX_NL_SENS_LDS(NS, NB) (8 * 3 * MCPX_NL_NV + (NS) * (8 * (NB) + 7) + 512)
+#define MCPX_NL_SENS_FITS(NS, NB) \
+  ((NS) >= 1 && (NB) <= MCPX_NL_SENS_NB_MAX && MCPX_NL_SENS_LDS(NS, NB) <= MCPX_NL_WG_LIMIT)
+#define MCPX_NL_SENS_NB(NS) \
+  (MCPX_NL_SENS_FITS(NS, 16) ? 16 : (MCPX_NL_SENS_FITS(NS, 8) ? 8 : (MCPX_NL_SENS_FITS(NS, 4) ? 4 : 0)))
+#define MCPX_NL_SENS_NB_VJP MCPX_NL_SENS_NB(MCPX_NL_N + MCPX_NL_M)
+#define MCPX_NL_SENS_NB_JVP MCPX_NL_SENS_NB(MCPX_NL_NV)
+
 #include "sens_wg_impl.hpp"
 #include "ipm_nl_band.hpp"
 
@@ -1027,8 +1044,8 @@ constexpr int NVW = imax(1, N);
 // mcpx_nl_meta: {layout version, n, m, p, has_s, kernel mask, block size, nnz, nnz of ∇F_θ,
 // the band kernel's workspace doubles per slot, 0, 0}; kernel mask: bit MCPX_LINSOLVE_* = one-wave kernel, bit 3 + MCPX_LINSOLVE_* =
 // workgroup kernel, bit MCPX_MODULE_VJP / MCPX_MODULE_JVP = sensitivity kernels (the
-// VJP factors the (n+m)-dim system of the REDUCED workgroup solver, the JVP the full
-// (n+2m)-dim ∇F_z of the DENSE one: they exist when those fit LDS), bit MCPX_MODULE_SCHUR_MW =
+// VJP factors an (n+m)-dim system, the JVP the full (n+2m)-dim ∇F_z: they exist when a panel
+// of 16, 8 or 4 columns of that system fits LDS, MCPX_NL_SENS_NB_VJP / _JVP above), bit MCPX_MODULE_SCHUR_MW =
 // the 4-wave SCHUR kernel mcpx_nl_solve_schur_mw (layout 4); bits MCPX_MODULE_BAND /
 // MCPX_MODULE_BAND_AUTO = the band SCHUR kernel mcpx_nl_solve_band (ipm_nl_band.hpp) and whether
 // MCPX_KERNEL_AUTO prefers it (both decided by codegen.py: MCPX_NL_CAN_BAND, MCPX_NL_BAND_AUTO)
@@ -1038,7 +1055,7 @@ __device__ int32_t mcpx_nl_meta[12] = {
     (MCPX_NL_CAN_REDUCED << MCPX_LINSOLVE_REDUCED) | (MCPX_NL_CAN_DENSE << MCPX_LINSOLVE_DENSE) |
         (MCPX_NL_CAN_SCHUR << MCPX_LINSOLVE_SCHUR) | (MCPX_NL_CAN_WG_REDUCED << (3 + MCPX_LINSOLVE_REDUCED)) |
         (MCPX_NL_CAN_WG_DENSE << (3 + MCPX_LINSOLVE_DENSE)) | (MCPX_NL_CAN_WG_SCHUR << (3 + MCPX_LINSOLVE_SCHUR)) |
-        (MCPX_NL_CAN_WG_REDUCED << MCPX_MODULE_VJP) | (MCPX_NL_CAN_WG_DENSE << MCPX_MODULE_JVP) |
+        ((MCPX_NL_SENS_NB_VJP != 0) << MCPX_MODULE_VJP) | ((MCPX_NL_SENS_NB_JVP != 0) << MCPX_MODULE_JVP) |
         (MCPX_NL_CAN_SCHUR_MW << MCPX_MODULE_SCHUR_MW) | (MCPX_NL_CAN_BAND << MCPX_MODULE_BAND) |
         ((MCPX_NL_CAN_BAND && MCPX_NL_BAND_AUTO) << MCPX_MODULE_BAND_AUTO),
     MCPX_NL_SIZE, MCPX_NL_NNZ, MCPX_NL_NNZ_T,
@@ -1051,14 +1068,22 @@ __device__ int32_t mcpx_nl_meta[12] = {
 
 // MCPX_NL_ONLY_BAND (experiments, never set by codegen.py): compile the band kernel alone
 #ifndef MCPX_NL_ONLY_BAND
-#if MCPX_NL_CAN_WG_REDUCED
+#if MCPX_NL_SENS_NB_VJP
+static_assert(sizeof(mcpx::wg::SolveShared<mcpx::nl::NVW, MCPX_NL_N + MCPX_NL_M, false, false, MCPX_NL_SENS_NB_VJP>) <=
+                  MCPX_NL_SENS_LDS(MCPX_NL_N + MCPX_NL_M, MCPX_NL_SENS_NB_VJP),
+              "MCPX_NL_SENS_LDS bounds the pullback kernel's LDS");
 __global__ __launch_bounds__(mcpx::wg::kThreads) void mcpx_nl_vjp_wg(const mcpx::wg::WgSensArgs args) {
-  mcpx::wg::sens_instances<MCPX_FAMILY_NONLINEAR, false, mcpx::nl::NVW, MCPX_NL_N + MCPX_NL_M, mcpx::nl::Gen>(args);
+  mcpx::wg::sens_instances<MCPX_FAMILY_NONLINEAR, false, mcpx::nl::NVW, MCPX_NL_N + MCPX_NL_M, mcpx::nl::Gen,
+                           MCPX_NL_SENS_NB_VJP>(args);
 }
 #endif
-#if MCPX_NL_CAN_WG_DENSE
+#if MCPX_NL_SENS_NB_JVP
+static_assert(sizeof(mcpx::wg::SolveShared<mcpx::nl::NVW, mcpx::nl::NVW, false, false, MCPX_NL_SENS_NB_JVP>) <=
+                  MCPX_NL_SENS_LDS(MCPX_NL_NV, MCPX_NL_SENS_NB_JVP),
+              "MCPX_NL_SENS_LDS bounds the tangent kernel's LDS");
 __global__ __launch_bounds__(mcpx::wg::kThreads) void mcpx_nl_jvp_wg(const mcpx::wg::WgSensArgs args) {
-  mcpx::wg::sens_instances<MCPX_FAMILY_NONLINEAR, true, mcpx::nl::NVW, mcpx::nl::NVW, mcpx::nl::Gen>(args);
+  mcpx::wg::sens_instances<MCPX_FAMILY_NONLINEAR, true, mcpx::nl::NVW, mcpx::nl::NVW, mcpx::nl::Gen,
+                           MCPX_NL_SENS_NB_JVP>(args);
 }
 #endif
 

@@ -17,7 +17,7 @@
 //   * implicit pivoting: rows are never moved; the remaining rows are kept as a
 //     list in ascending row order, and the pivot of column k is the first
 //     remaining row of largest |a_ik| (NaN never wins; all-NaN → first row);
-//   * panel of NB = 16 columns staged in LDS and factored column by column
+//   * panel of NB columns (16; 8 or 4 where 16 do not fit the LDS) staged in LDS and factored column by column
 //     (multipliers l_i = a_ik / pivot, a_ij ← fma(−l_i, u_j, a_ij));
 //   * the panel's pivot rows get their trailing part (U12, the rhs included) by
 //     the in-panel forward substitution — the same fma chain the unblocked
@@ -46,7 +46,7 @@ namespace wg {
 
 constexpr int WG = kThreads;  // threads per workgroup
 constexpr int NWAVE = WG / 64;
-constexpr int NB = 16;   // LU panel width
+constexpr int kNB = 16;  // LU panel width (the default; narrower panels: LuShared below)
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -141,8 +141,15 @@ __device__ __forceinline__ uint64_t pivot_key(double a) {
 // same elimination); destroyed.  x (LDS, ≥ ns): the solution of the last right-hand side,
 // x[k] = δz_k; with xout, the solution of right-hand side c is also stored at
 // xout[c·ns + k] (the sensitivity kernels' several partials).
-template <int NSMAX>
+//
+// NB (16, 8 or 4) is the panel width: how many elimination steps an entry takes between two
+// trips to HBM.  Every entry sees the same k-ascending fma chain at every width (an fp64 store
+// and reload rounds nothing), so the width changes the LDS footprint and the speed, not a bit
+// of the result.  The MFMA tiles stay 16 × 16; a full panel is NB / 4 K-chunks.
+template <int NSMAX, int NB = kNB>
 struct LuShared {
+  static_assert(NB == 16 || NB == 8 || NB == 4, "panel width: whole K-chunks of the 16x16x4 MFMA");
+  static_assert(NSMAX <= 32767, "the row lists (rem, step_of, prow, pivpos) are int16_t");
   double pan[NSMAX * NB];     // the panel, row q = remaining-list position q
   double bb[NB];              // back substitution: rhs of the block's pivot rows
   uint64_t key[2][NWAVE];     // pivot search, double-buffered by step parity
@@ -159,8 +166,8 @@ struct LuShared {
 // rows q ≡ tid (mod 256) for the whole panel (their updates and pivot flags are
 // its own), so the only cross-thread data of a step are the 4 wave maxima and the
 // pivot row, both published before the barrier of the step's search.
-template <int NSMAX>
-__device__ __forceinline__ int panel_pivot(LuShared<NSMAX>& L, int r, int kk, int step) {
+template <int NSMAX, int NB>
+__device__ __forceinline__ int panel_pivot(LuShared<NSMAX, NB>& L, int r, int kk, int step) {
   const int tid = threadIdx.x, wave = tid >> 6;
   uint64_t key = 0;
   int pos = -1;
@@ -186,8 +193,8 @@ __device__ __forceinline__ int panel_pivot(LuShared<NSMAX>& L, int r, int kk, in
 
 // RCP: the reciprocal-multiplier arithmetic of oracle lu_solve_x (rcp = 1; the SCHUR step of
 // generated nonlinear modules): l = a_ik · (1 / piv), x_k = b_p · (1 / u_kk).
-template <int NSMAX, bool RCP = false>
-__device__ __forceinline__ bool lu_solve(double* __restrict__ A, int ld, int ns, double* x, LuShared<NSMAX>& L,
+template <int NSMAX, bool RCP = false, int NB = kNB>
+__device__ __forceinline__ bool lu_solve(double* __restrict__ A, int ld, int ns, double* x, LuShared<NSMAX, NB>& L,
                                          int nrhs = 1, double* __restrict__ xout = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int i = tid; i < ns; i += WG) L.rem[i] = (int16_t)i;
@@ -272,7 +279,7 @@ __device__ __forceinline__ bool lu_solve(double* __restrict__ A, int ld, int ns,
           acc[e] = (rin[e] && jin) ? A[rowo[e] + j] : 0.0;
         }
         const int pa = 16 * ti + lc;  // A-fragment row of this lane
-        if (kb == NB) {  // the common full panel: 4 K-chunks, loads hoisted ahead of the MFMA chain
+        if (kb == NB) {  // the common full panel: NB / 4 K-chunks, loads hoisted ahead of the MFMA chain
           double av[NB / 4], bv[NB / 4];
 #pragma unroll
           for (int c = 0; c < NB / 4; ++c) {
@@ -331,11 +338,11 @@ __device__ __forceinline__ bool lu_solve(double* __restrict__ A, int ld, int ns,
     r = base;
     __syncthreads();
   }
-  // ---- back substitution, blocked by 16 columns ---------------------------------
+  // ---- back substitution, blocked by NB columns ---------------------------------
   // Oracle order: row i takes fma(−u_ik, x_k, b_i) for k = ns−1 down to step_of(i)+1.
-  // Per block [k0, k0+16), descending: wave 0 solves the block's 16 pivot rows
+  // Per block [k0, k0+NB), descending: wave 0 solves the block's NB pivot rows
   // (each already updated by every later block) serially in registers, then every
-  // row of an earlier step takes the block's 16 updates, k descending.
+  // row of an earlier step takes the block's NB updates, k descending.
   constexpr int RPT = (NSMAX + WG - 1) / WG;  // rows per thread (rows i ≡ tid mod 256)
   double b[RPT];
   int st[RPT];
@@ -542,10 +549,10 @@ union VrGjShared {
   GjShared<NSMAX> gj;
 };
 
-template <int NVMAX, int NSMAX, bool VR = kVr<NSMAX>, bool GJ = false>
+template <int NVMAX, int NSMAX, bool VR = kVr<NSMAX>, bool GJ = false, int NB = kNB>
 struct SolveShared {
   double zs[NVMAX], Fs[NVMAX], dzs[NVMAX];
-  std::conditional_t<GJ, VrGjShared<NSMAX>, std::conditional_t<VR, VrShared<NSMAX, 1>, LuShared<NSMAX>>> lu;
+  std::conditional_t<GJ, VrGjShared<NSMAX>, std::conditional_t<VR, VrShared<NSMAX, 1>, LuShared<NSMAX, NB>>> lu;
   Scratch sc;
 };
 

@@ -801,8 +801,8 @@ int prepare_sens(const mcpx_desc* d, mcpx::SensArgs* a, SensPlan* plan, bool jvp
   if (mod) {
     const int bit = jvp ? MCPX_MODULE_JVP : MCPX_MODULE_VJP;
     if (!((mod->meta[5] >> bit) & 1))
-      return fail(MCPX_EUNSUPPORTED, "the generated module has no %s kernel (n=%d m=%d: its LDS footprint does not fit)",
-                  jvp ? "JVP" : "VJP", d->n, d->m);
+      return fail(MCPX_EUNSUPPORTED, "the generated module has no %s kernel (n=%d m=%d: not even a 4-column LU panel of "
+                  "its %d-row system fits the LDS)", jvp ? "JVP" : "VJP", d->n, d->m, jvp ? N : d->n + d->m);
     plan->wg = true;
   } else if (N <= MCPX_MAX_KKT_DIM) {
     plan->nmax = pick_nmax(N);
@@ -861,7 +861,11 @@ int launch_sens_wg_impl(bool jvp, const mcpx_desc* d, mcpx::SensArgs a, const Se
   w.off_sol = align(w.off_dth + (plan.mod ? (int64_t)nr * a.p : 0));
   w.slot_stride = align(w.off_sol + (jvp ? (int64_t)nrhs * ns : 0));
   const int64_t CH = (int64_t)1 << 30;
-  const int64_t grid_max = std::min(slots_max, std::min(CH, d->batch));
+  int64_t grid_max = std::min(slots_max, std::min(CH, d->batch));
+  // a long-horizon module's slot is tens of MB (T = 30 tangents: 35 MB of [K | rhs] alone): the
+  // persistent grid takes at most 4 GiB of workspace, fewer workgroups on the same queue
+  const int64_t ws_cap = ((int64_t)4 << 30) / (int64_t)sizeof(double);
+  if (grid_max * w.slot_stride > ws_cap) grid_max = std::max<int64_t>(1, ws_cap / w.slot_stride);
   double* ws = nullptr;
   const size_t bytes = sizeof(double) * (size_t)(grid_max * w.slot_stride) + 256;
   HIP_TRY(dev_alloc((void**)&ws, bytes, st));

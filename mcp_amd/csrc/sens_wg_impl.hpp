@@ -126,8 +126,8 @@ __device__ __forceinline__ double dtheta_entry(int64_t t, const double* lam, con
 // (sums, sign vector, argmax) run on thread 0 in the oracle's order.
 
 // A x = b: b (row-indexed) destroyed, x (column-indexed).
-template <int NSMAX>
-__device__ __forceinline__ void lu_apply(const double* __restrict__ A, int ld, int N, const LuShared<NSMAX>& L,
+template <int NSMAX, int NB>
+__device__ __forceinline__ void lu_apply(const double* __restrict__ A, int ld, int N, const LuShared<NSMAX, NB>& L,
                                          double* b, double* x) {
   const int tid = threadIdx.x;
   for (int k = 0; k < N; ++k) {
@@ -147,8 +147,8 @@ __device__ __forceinline__ void lu_apply(const double* __restrict__ A, int ld, i
 }
 
 // Aᵀ z = c (PA = LU): c (column-indexed) destroyed, u (N scratch), z (row-indexed).
-template <int NSMAX>
-__device__ __forceinline__ void lu_apply_t(const double* __restrict__ A, int ld, int N, const LuShared<NSMAX>& L,
+template <int NSMAX, int NB>
+__device__ __forceinline__ void lu_apply_t(const double* __restrict__ A, int ld, int N, const LuShared<NSMAX, NB>& L,
                                            double* c, double* u, double* z) {
   const int tid = threadIdx.x;
   for (int k = 0; k < N; ++k) {  // Uᵀ
@@ -168,8 +168,8 @@ __device__ __forceinline__ void lu_apply_t(const double* __restrict__ A, int ld,
 }
 
 // rcond of the N×N ∇F_z in A (destroyed); v0..v2: LDS vectors, h: 2·N doubles of HBM scratch.
-template <int NSMAX>
-__device__ __forceinline__ double cond_one(double* __restrict__ A, int ld, int N, LuShared<NSMAX>& L, double* v0,
+template <int NSMAX, int NB>
+__device__ __forceinline__ double cond_one(double* __restrict__ A, int ld, int N, LuShared<NSMAX, NB>& L, double* v0,
                                            double* v1, double* v2, double* h, double* xs, Scratch& sc, bool& singular) {
   const int tid = threadIdx.x;
   for (int j = tid; j < N; j += WG) {  // column sums of |a_ij|, rows ascending
@@ -187,7 +187,7 @@ __device__ __forceinline__ double cond_one(double* __restrict__ A, int ld, int N
     }
   }
   __syncthreads();
-  singular = !lu_solve<NSMAX>(A, ld, N, xs, L, 0, nullptr);
+  singular = !lu_solve<NSMAX, false, NB>(A, ld, N, xs, L, 0, nullptr);
   if (singular) return 0.0;
   double* const x = v0;   // the rhs of the next solve (destroyed by it)
   double* const y = v1;   // A⁻¹x
@@ -200,7 +200,7 @@ __device__ __forceinline__ double cond_one(double* __restrict__ A, int ld, int N
   double est = 0.0;  // thread 0 holds the estimate; the stop decisions go through sc.i[0]
   int jprev = -1;
   for (int it = 0; it < 5; ++it) {
-    lu_apply<NSMAX>(A, ld, N, L, x, y);
+    lu_apply(A, ld, N, L, x, y);
     if (tid == 0) {
       double g = 0.0;
       for (int k = 0; k < N; ++k) g = g + fabs(y[k]);
@@ -221,7 +221,7 @@ __device__ __forceinline__ double cond_one(double* __restrict__ A, int ld, int N
     if (sc.i[0]) break;
     for (int k = tid; k < N; k += WG) x[k] = xi[k];
     __syncthreads();
-    lu_apply_t<NSMAX>(A, ld, N, L, x, u, z);
+    lu_apply_t(A, ld, N, L, x, u, z);
     if (tid == 0) {
       int jm = -1;
       double bz = -1.0;
@@ -244,7 +244,7 @@ __device__ __forceinline__ double cond_one(double* __restrict__ A, int ld, int N
   }
   for (int i = tid; i < N; i += WG) x[i] = (i & 1 ? -1.0 : 1.0) * (1.0 + (N > 1 ? (double)i / (double)(N - 1) : 0.0));
   __syncthreads();
-  lu_apply<NSMAX>(A, ld, N, L, x, y);
+  lu_apply(A, ld, N, L, x, y);
   double rc = 0.0;
   if (tid == 0) {
     double g = 0.0;
@@ -257,10 +257,12 @@ __device__ __forceinline__ double cond_one(double* __restrict__ A, int ld, int N
   return rc;  // thread 0's
 }
 
-template <int FAMILY, bool JVP, int NVMAX, int NSMAX, class GEN>
+// NB: the panel width of the blocked LU (wg::LuShared); generated modules whose 16-column panel
+// does not fit the LDS pass 8 or 4 (csrc/ipm_nl_kernel.hpp, MCPX_NL_SENS_NB_*).
+template <int FAMILY, bool JVP, int NVMAX, int NSMAX, class GEN, int NB = kNB>
 __device__ __forceinline__ void sens_instances(const WgSensArgs& W) {
   constexpr bool NL = FAMILY == MCPX_FAMILY_NONLINEAR;
-  __shared__ SolveShared<NVMAX, NSMAX, false> S;  // several right-hand sides: the HBM LU
+  __shared__ SolveShared<NVMAX, NSMAX, false, false, NB> S;  // several right-hand sides: the HBM LU
   const SensArgs& a = W.s;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = a.n, m = a.m, N = n + 2 * m, nr = n + m;
@@ -308,7 +310,7 @@ __device__ __forceinline__ void sens_instances(const WgSensArgs& W) {
           for (int j = lane; j < N; j += 64) Am[(int64_t)r * ld + j] = jac<FAMILY, GEN>(th, blk, zs, n, m, r, j);
         __syncthreads();
         bool sing = false;
-        const double rc = cond_one<NSMAX>(Am, ld, N, S.lu, S.zs, S.Fs, S.dzs, sol, xs, S.sc, sing);
+        const double rc = cond_one(Am, ld, N, S.lu, S.zs, S.Fs, S.dzs, sol, xs, S.sc, sing);
         if (tid == 0) {
           a.out[inst] = rc;
           if (a.status) a.status[inst] = sing ? 1 : 0;
@@ -354,7 +356,7 @@ __device__ __forceinline__ void sens_instances(const WgSensArgs& W) {
       }
       __syncthreads();
       // ---- LU with partial pivoting (oracle lu_solve) -------------------------------
-      const bool ok = lu_solve<NSMAX>(Am, ld, ns, xs, S.lu, R, JVP ? sol : nullptr);
+      const bool ok = lu_solve<NSMAX, false, NB>(Am, ld, ns, xs, S.lu, R, JVP ? sol : nullptr);
       ok_all = ok_all && ok;
       if constexpr (JVP) {
         for (int c = 0; c < R; ++c)

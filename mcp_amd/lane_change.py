@@ -194,6 +194,19 @@ class LaneChangeGame:
         return out
 
 
-def prebuild(horizons=(2,), verbose: bool = False) -> list:
-    """Compile the C4 modules ahead of time (in-tree, by __graft_entry__.build())."""
-    return [LaneChangeGame(T).mcp.nl.build_module(verbose=verbose) for T in horizons]
+def prebuild(horizons=(2,), verbose: bool = False, capped=(), extra=()) -> list:
+    """Compile the C4 modules ahead of time (in-tree, by __graft_entry__.build()).  capped:
+    (horizon, sens_panel_max) pairs, the modules whose sensitivity kernels run a narrower panel
+    than fits (backend_options "sens_panel_max"); extra: callables returning further MCPs with
+    a generated module.  The compiles run side by side (codegen.build_modules)."""
+    from . import codegen
+
+    def systems():
+        for T in horizons:
+            yield LaneChangeGame(T).mcp.nl
+        for T, cap in capped:
+            yield LaneChangeGame(T, backend_options={"sens_panel_max": cap}).mcp.nl
+        for make in extra:
+            yield make().nl
+
+    return codegen.build_modules(systems(), verbose=verbose)

@@ -24,7 +24,9 @@ def main() -> int:
     from tests.test_nonlinear import cubic_mcp, trig_mcp
     from tests.test_sensitivity_nl import poly_mcp
 
-    nls = [LaneChangeGame(T).mcp.nl for T in (2, 10)] + [m.nl for m in (cubic_mcp(), trig_mcp(), poly_mcp(40, 30))]
+    nls = [LaneChangeGame(T).mcp.nl for T in (2, 10, 12, 15, 21)]
+    nls += [LaneChangeGame(2, backend_options={"sens_panel_max": cap}).mcp.nl for cap in (8, 4)]
+    nls += [m.nl for m in (cubic_mcp(), trig_mcp(), poly_mcp(40, 30))]
     for nl in nls:
         p = nl.module_path()
         if not os.path.exists(p):
