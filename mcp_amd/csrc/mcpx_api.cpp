@@ -24,20 +24,38 @@
 #include <vector>
 
 #include "../../include/mcpx.h"
+#include "dev_pool.hpp"
 #include "ipm_kernel.h"
 #include "ipm_wg.h"
 #include "sens_kernel.h"
+#include "wg_layout.h"
+
+// Fields of the record mcpx_nl_meta that a generated module exports (defined, with the
+// kernel mask's bits, at the end of csrc/ipm_nl_kernel.hpp).
+enum NLMeta {
+  kMetaLayout = 0,   // layout version: kNLLayout
+  kMetaN = 1,
+  kMetaM = 2,
+  kMetaP = 3,        // θ dimension
+  kMetaKernels = 5,  // kernel mask
+  kMetaBlock = 6,    // doubles of the generated Jacobian blocks (MCPX_NL_SIZE)
+  kMetaBandWs = 9,   // the band kernel's workspace doubles per slot
+};
+constexpr int32_t kNLLayout = 4;
 
 // A generated nonlinear module (MCPX_FAMILY_NONLINEAR, include/mcpx.h): the
 // code object image, its metadata record and the per-device loaded modules.
 struct mcpx_module {
   std::vector<char> image;
-  int32_t meta[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // mcpx_nl_meta of csrc/ipm_nl_kernel.hpp
+  int32_t meta[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // indexed by NLMeta
   std::mutex mu;
   std::map<int, hipModule_t> loaded;  // device → module, loaded on first use
+  bool has(int bit) const { return (meta[kMetaKernels] >> bit) & 1; }  // a bit of the kernel mask
 };
 
 namespace {
+
+namespace wg = mcpx::wg;
 
 thread_local std::string g_err;
 
@@ -93,41 +111,56 @@ int pick_nmax(int N) {
 
 // Smallest workgroup-kernel vector-dimension bucket ≥ N (QP / affine), or -1.
 int pick_wg_bucket(int N) {
-  for (int w : mcpx::wg::kDimBuckets)
+  for (int w : wg::kDimBuckets)
     if (N <= w) return w;
   return -1;
 }
 
-// Validates desc/params and fills the scalar part + tables of the kernel args.
-// *wg: the solve runs on the workgroup-per-instance kernels (ipm_wg_impl.hpp);
-// *nmax: the one-wave kernels' row width, or the workgroup kernels' dimension bucket.
-int prepare(const mcpx_desc* d, const mcpx_params* p, mcpx::KernelArgs* a, int* nmax,
-            const mcpx_module* mod = nullptr, bool* wg = nullptr, bool* mw = nullptr, bool* band = nullptr) {
-  bool wg_local = false, mw_local = false, band_local = false;
-  if (!wg) wg = &wg_local;
-  if (!mw) mw = &mw_local;
-  if (!band) band = &band_local;
-  *mw = false;
-  *band = false;
-  if (!d || !p) return fail(MCPX_EINVAL, "desc and params must be non-NULL");
-  int64_t pd;
+// What a call does with a generated module, for the two messages of check_desc that say so.
+struct Wording {
+  const char *does, *goes, *entry;
+};
+constexpr Wording kSolveWords = {"solves", "runs", "mcpx_solve_batch_module*"};
+constexpr Wording kSensWords = {"differentiates", "is differentiated", "mcpx_vjp_batch_module / mcpx_jvp_batch_module"};
+
+// The descriptor checks shared by the solves and the sensitivities; *pd: the θ dimension
+// (of the family, or of the generated module `mod`).
+int check_desc(const mcpx_desc* d, const mcpx_module* mod, int64_t* pd, const Wording& w) {
   if (mod) {  // a generated nonlinear module: θ dimension and sizes from its metadata
     if (d->family != MCPX_FAMILY_NONLINEAR)
-      return fail(MCPX_EINVAL, "a generated module solves family MCPX_FAMILY_NONLINEAR (got %d)", d->family);
-    if (d->n != mod->meta[1] || d->m != mod->meta[2])
+      return fail(MCPX_EINVAL, "a generated module %s family MCPX_FAMILY_NONLINEAR (got %d)", w.does, d->family);
+    if (d->n != mod->meta[kMetaN] || d->m != mod->meta[kMetaM])
       return fail(MCPX_EINVAL, "desc (n=%d, m=%d) does not match the module (n=%d, m=%d)", d->n, d->m,
-                  mod->meta[1], mod->meta[2]);
-    pd = mod->meta[3];
+                  mod->meta[kMetaN], mod->meta[kMetaM]);
+    *pd = mod->meta[kMetaP];
   } else {
     if (d->family == MCPX_FAMILY_NONLINEAR)
-      return fail(MCPX_EINVAL, "family MCPX_FAMILY_NONLINEAR runs through its generated module "
-                  "(mcpx_solve_batch_module*)");
-    pd = mcpx_theta_dim(d->family, d->n, d->m);
+      return fail(MCPX_EINVAL, "family MCPX_FAMILY_NONLINEAR %s through its generated module (%s)", w.goes, w.entry);
+    *pd = mcpx_theta_dim(d->family, d->n, d->m);
   }
-  if (pd < 0) return fail(MCPX_EINVAL, "bad family %d or negative dimensions (n=%d, m=%d)", d->family, d->n, d->m);
+  if (*pd < 0) return fail(MCPX_EINVAL, "bad family %d or negative dimensions (n=%d, m=%d)", d->family, d->n, d->m);
   if (d->n + d->m < 1) return fail(MCPX_EINVAL, "empty problem (n = m = 0)");
   if (d->batch < 0) return fail(MCPX_EINVAL, "negative batch");
-  if (d->theta_ld < pd) return fail(MCPX_EINVAL, "theta_ld %lld < parameter dimension %lld", (long long)d->theta_ld, (long long)pd);
+  if (d->theta_ld < *pd) return fail(MCPX_EINVAL, "theta_ld %lld < parameter dimension %lld", (long long)d->theta_ld, (long long)*pd);
+  return MCPX_OK;
+}
+
+// How a solve runs: the one-wave kernels (`nmax`: their row width), the workgroup-per-instance
+// kernels (wg; ipm_wg_impl.hpp, `nmax`: their dimension bucket), or a generated module's
+// (`mod`) one-wave, workgroup, multi-wave (mw) or band kernel.
+struct SolvePlan {
+  int nmax = 0;
+  bool wg = false, mw = false, band = false;
+  mcpx_module* mod = nullptr;
+};
+
+// Validates desc/params; fills the scalar part + tables of the kernel args and the plan.
+int prepare(const mcpx_desc* d, const mcpx_params* p, mcpx::KernelArgs* a, SolvePlan* plan, mcpx_module* mod) {
+  *plan = SolvePlan{};
+  plan->mod = mod;
+  if (!d || !p) return fail(MCPX_EINVAL, "desc and params must be non-NULL");
+  int64_t pd;
+  if (const int rc = check_desc(d, mod, &pd, kSolveWords)) return rc;
   const int ls = p->linear_solver;
   if (ls != MCPX_LINSOLVE_REDUCED && ls != MCPX_LINSOLVE_DENSE && ls != MCPX_LINSOLVE_SCHUR)
     return fail(MCPX_EINVAL, "unknown linear_solver %d", ls);
@@ -136,37 +169,37 @@ int prepare(const mcpx_desc* d, const mcpx_params* p, mcpx::KernelArgs* a, int* 
     return fail(MCPX_EINVAL, "unknown kernel selector %d", p->kernel);
   bool wave_ok, wg_ok;
   if (mod) {
-    wave_ok = (mod->meta[5] >> ls) & 1;
-    wg_ok = (mod->meta[5] >> (3 + ls)) & 1;
-    const bool mw_ok = ls == MCPX_LINSOLVE_SCHUR && ((mod->meta[5] >> MCPX_MODULE_SCHUR_MW) & 1);
+    wave_ok = mod->has(ls);
+    wg_ok = mod->has(3 + ls);
+    const bool mw_ok = ls == MCPX_LINSOLVE_SCHUR && mod->has(MCPX_MODULE_SCHUR_MW);
     if (p->kernel == MCPX_KERNEL_MULTIWAVE && !mw_ok)
       return fail(MCPX_EUNSUPPORTED, "the generated module has no multi-wave kernel for linear_solver=%d", ls);
-    *mw = mw_ok && p->kernel == MCPX_KERNEL_MULTIWAVE;  // measured slower than one wave: opt-in
+    plan->mw = mw_ok && p->kernel == MCPX_KERNEL_MULTIWAVE;  // measured slower than one wave: opt-in
     // the band kernel (ipm_nl_band.hpp): forced, or AUTO when the module prefers it or has no
     // one-wave SCHUR kernel (oracle/ipm_oracle.c picks lu_band_solve by the same rule)
-    const bool band_ok = ls == MCPX_LINSOLVE_SCHUR && ((mod->meta[5] >> MCPX_MODULE_BAND) & 1);
-    const bool band_auto = band_ok && ((mod->meta[5] >> MCPX_MODULE_BAND_AUTO) & 1);
+    const bool band_ok = ls == MCPX_LINSOLVE_SCHUR && mod->has(MCPX_MODULE_BAND);
+    const bool band_auto = band_ok && mod->has(MCPX_MODULE_BAND_AUTO);
     if (p->kernel == MCPX_KERNEL_BAND && !band_ok)
       return fail(MCPX_EUNSUPPORTED, "the generated module has no band kernel for linear_solver=%d", ls);
-    *band = p->kernel == MCPX_KERNEL_BAND || (p->kernel == MCPX_KERNEL_AUTO && band_ok && (band_auto || !wave_ok));
-    *nmax = 0;
+    plan->band = p->kernel == MCPX_KERNEL_BAND || (p->kernel == MCPX_KERNEL_AUTO && band_ok && (band_auto || !wave_ok));
   } else {
     if (p->kernel == MCPX_KERNEL_MULTIWAVE)
       return fail(MCPX_EUNSUPPORTED, "MCPX_KERNEL_MULTIWAVE is a generated module's SCHUR kernel");
     if (p->kernel == MCPX_KERNEL_BAND)
       return fail(MCPX_EUNSUPPORTED, "MCPX_KERNEL_BAND is a generated module's SCHUR kernel");
-    // (affine family: ∂H/∂y is taken as 0 — the S block of θ' is not read, include/mcpx.h)
+    // (affine family, SCHUR: the S block of θ (∂H/∂y) is read, and a nonzero or NaN entry ends the
+    // instance with MCPX_FAIL_INPUT, include/mcpx.h)
     const int N = ls == MCPX_LINSOLVE_DENSE ? d->n + 2 * d->m : (ls == MCPX_LINSOLVE_REDUCED ? d->n + d->m : d->n);
     const int lanes = ls == MCPX_LINSOLVE_DENSE ? d->n + 2 * d->m : d->n + d->m;  // one wave: one lane per row
     wave_ok = pick_nmax(N) > 0 && lanes <= MCPX_MAX_KKT_DIM;
     // workgroup kernels: REDUCED / DENSE, and SCHUR for the QP family up to n = 128 (gj_vr.hpp)
-    wg_ok = (ls != MCPX_LINSOLVE_SCHUR || (d->family == MCPX_FAMILY_QP && d->n <= mcpx::wg::kGjMax)) &&
+    wg_ok = (ls != MCPX_LINSOLVE_SCHUR || (d->family == MCPX_FAMILY_QP && d->n <= wg::kGjMax)) &&
             d->n + 2 * d->m <= MCPX_MAX_WG_KKT_DIM;
-    *nmax = wave_ok && p->kernel != MCPX_KERNEL_WORKGROUP ? pick_nmax(N) : pick_wg_bucket(d->n + 2 * d->m);
+    plan->nmax = wave_ok && p->kernel != MCPX_KERNEL_WORKGROUP ? pick_nmax(N) : pick_wg_bucket(d->n + 2 * d->m);
   }
   if (p->kernel == MCPX_KERNEL_WAVE) wg_ok = false;
   if (p->kernel == MCPX_KERNEL_WORKGROUP) wave_ok = false;
-  if (*mw || *band) wave_ok = true;
+  if (plan->mw || plan->band) wave_ok = true;
   if (!wave_ok && !wg_ok) {
     if (mod)
       return fail(MCPX_EUNSUPPORTED, "the generated module has no %s kernel for linear_solver=%d (n=%d m=%d)",
@@ -175,9 +208,9 @@ int prepare(const mcpx_desc* d, const mcpx_params* p, mcpx::KernelArgs* a, int* 
     return fail(MCPX_EUNSUPPORTED, "problem size n=%d m=%d, linear_solver=%d exceeds the kernels (one wave: "
                 "reduced/schur n+m <= %d, dense n+2m <= %d; workgroup: reduced/dense n+2m <= %d, "
                 "schur: QP family, n <= %d)",
-                d->n, d->m, ls, MCPX_MAX_KKT_DIM, MCPX_MAX_KKT_DIM, MCPX_MAX_WG_KKT_DIM, mcpx::wg::kGjMax);
+                d->n, d->m, ls, MCPX_MAX_KKT_DIM, MCPX_MAX_KKT_DIM, MCPX_MAX_WG_KKT_DIM, wg::kGjMax);
   }
-  *wg = !wave_ok;
+  plan->wg = !wave_ok;
   if (!(p->tol > 0) || !(p->min_stepsize > 0) || !(p->decay > 0 && p->decay < 1) || std::isnan(p->tau) ||
       std::isnan(p->tightening_rate) || std::isnan(p->loosening_rate) || p->max_inner_iters < 1 ||
       p->max_outer_iters < 1)
@@ -213,7 +246,6 @@ int prepare(const mcpx_desc* d, const mcpx_params* p, mcpx::KernelArgs* a, int* 
 }
 
 // ---- generated nonlinear modules ---------------------------------------------
-constexpr int32_t kNLLayout = 4;  // mcpx_nl_meta[0] of csrc/ipm_nl_kernel.hpp
 const char* const kNLKernel[3] = {"mcpx_nl_solve_reduced", "mcpx_nl_solve_dense", "mcpx_nl_solve_schur"};
 
 // `mod` on device `dev` (the current device), loaded on first use.
@@ -229,18 +261,29 @@ int module_on(mcpx_module* mod, int dev, hipModule_t* hm) {
   return MCPX_OK;
 }
 
-// The module's kernel for linear solver `solver` (one-wave, or the workgroup
-// kernel "<name>_wg") on the current device.
-int nl_function(mcpx_module* mod, int solver, bool wg, hipFunction_t* f, bool mw = false) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
+// The module's kernel `name` (`shown` in the message when it has none) on the current
+// device, *dev.
+int module_function(mcpx_module* mod, const char* name, const char* shown, hipFunction_t* f, int* dev) {
+  HIP_TRY(hipGetDevice(dev));
   hipModule_t hm;
-  const int rc = module_on(mod, dev, &hm);
+  const int rc = module_on(mod, *dev, &hm);
   if (rc) return rc;
-  const std::string name = std::string(kNLKernel[solver]) + (wg ? "_wg" : (mw ? "_mw" : ""));
-  if (hipModuleGetFunction(f, hm, name.c_str()) != hipSuccess)
-    return fail(MCPX_EUNSUPPORTED, "the generated module has no %s kernel", name.c_str());
+  if (hipModuleGetFunction(f, hm, name) != hipSuccess)
+    return fail(MCPX_EUNSUPPORTED, "the generated module has no %s kernel", shown);
   return MCPX_OK;
+}
+
+// The module's solve kernel for linear solver `solver`: one-wave (suffix ""), workgroup
+// ("_wg") or multi-wave ("_mw").
+int nl_function(mcpx_module* mod, int solver, const char* suffix, hipFunction_t* f) {
+  const std::string name = std::string(kNLKernel[solver]) + suffix;
+  int dev = 0;
+  return module_function(mod, name.c_str(), name.c_str(), f, &dev);
+}
+
+hipError_t launch_module(hipFunction_t f, int64_t grid, unsigned threads, void* args, hipStream_t st) {
+  void* params[] = {args};
+  return hipModuleLaunchKernel(f, (unsigned)grid, 1, 1, threads, 1, 1, 0, st, params, nullptr);
 }
 
 // Picks the kernel: a compile-time-(n, m) specialisation when one exists (and
@@ -286,134 +329,103 @@ void set_chunk(mcpx::KernelArgs& a, const mcpx_desc* d, const double* theta, con
   a.fail_reason = o->fail_reason ? o->fail_reason + b0 : nullptr;
 }
 
-hipError_t dev_alloc(void** p, size_t bytes, hipStream_t st);  // the library's block cache (below)
-void dev_release(void* p, hipStream_t st);
-
-// Workgroup-per-instance launch (ipm_wg_impl.hpp): a persistent grid of the
-// resident workgroups pulls instances from an atomic counter; each workgroup
-// slot owns a workspace in HBM ([K | rhs] row-major, and for a generated module
-// its Jacobian blocks), allocated stream-ordered for this call.
-int launch_wg(const mcpx_desc* d, const double* theta, const double* x0, const double* y0, const double* s0,
-              const mcpx_out* o, mcpx::KernelArgs a, int nv, hipStream_t st, mcpx_module* mod) {
-  const int n = d->n, m = d->m, ls = a.solver;
-  const int ns = ls == MCPX_LINSOLVE_SCHUR ? n : (ls == MCPX_LINSOLVE_REDUCED ? n + m : n + 2 * m);
+// A kernel of the persistent-grid launches: a generated module's function or a host symbol.
+struct GridKernel {
   hipFunction_t f = nullptr;
-  const void* kp = nullptr;
-  int per_cu = 0;
-  if (mod) {
-    const int rc = nl_function(mod, ls, true, &f);
-    if (rc) return rc;
-    HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, mcpx::wg::kThreads, 0));
-  } else {
-    kp = mcpx::ipm_wg_kernel(a.family, ls, nv, ns);
-    if (!kp) return fail(MCPX_EUNSUPPORTED, "no workgroup kernel for family %d, linear_solver %d, dim %d", a.family, ls, nv);
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, mcpx::wg::kThreads, 0));
-  }
-  int dev = 0, cus = 0;
-  HIP_TRY(hipGetDevice(&dev));
+  const void* sym = nullptr;
+  int threads = wg::kThreads;
+};
+
+// The persistent-grid launch of the workgroup-per-instance kernels and the band kernel: a
+// grid of the resident workgroups (occupancy × CUs of device `dev`; -1: the current one,
+// asked for here) pulls instances from an atomic counter; each workgroup slot owns
+// w.slot_stride doubles of workspace in HBM (at most `cap_bytes` in all, 0: no cap), allocated
+// stream-ordered for this call with the counter behind it.  `w` (WgArgs / WgSensArgs) gets
+// the workspace, the counter and each chunk's batch; launch(b0, grid) fills the rest for
+// the chunk that starts at instance b0 and launches `grid` workgroups.
+template <class W, class Launch>
+int launch_persistent(const GridKernel& k, int dev, int64_t batch, W& w, int64_t cap_bytes, hipStream_t st,
+                      const char* what, Launch&& launch) {
+  int per_cu = 0, cus = 0;
+  if (k.f)
+    HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.f, k.threads, 0));
+  else
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.sym, k.threads, 0));
+  if (dev < 0) HIP_TRY(hipGetDevice(&dev));
   HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const int64_t slots_max = (int64_t)std::max(per_cu, 1) * std::max(cus, 1);
-  auto align = [](int64_t v) { return (v + 31) / 32 * 32; };  // 256-B boundaries
-  mcpx::wg::WgArgs w{};
-  w.ld = ns + 1;
-  w.off_blk = align((int64_t)ns * w.ld);
-  w.off_aux = align(w.off_blk + (mod ? mod->meta[6] : 0));
-  w.off_rd = w.off_aux;  // (R·D⁻¹ no longer kept: the SCHUR entries read R and D⁻¹ directly)
-  w.slot_stride = align(w.off_aux + (ls == MCPX_LINSOLVE_SCHUR ? 4 * (int64_t)m : 0));
-  const int64_t CH = (int64_t)1 << 30;
-  const int64_t grid_max = std::min(slots_max, std::min(CH, d->batch));
-  double* ws = nullptr;
-  const size_t bytes = sizeof(double) * (size_t)(grid_max * w.slot_stride) + 256;
-  HIP_TRY(dev_alloc((void**)&ws, bytes, st));
-  w.work = ws;
-  w.counter = (int32_t*)(ws + grid_max * w.slot_stride);
+  const int64_t slots = (int64_t)std::max(per_cu, 1) * std::max(cus, 1);
+  const int64_t grid_max = wg::grid_size(slots, batch, w.slot_stride, cap_bytes);
+  HIP_TRY(dev_alloc((void**)&w.work, sizeof(double) * (size_t)(grid_max * w.slot_stride) + 256, st));
+  w.counter = (int32_t*)(w.work + grid_max * w.slot_stride);
   int rc = MCPX_OK;
-  for (int64_t b0 = 0; b0 < d->batch && rc == MCPX_OK; b0 += CH) {
-    const int64_t nb = std::min(CH, d->batch - b0);
-    const int grid = (int)std::min(grid_max, nb);
-    set_chunk(a, d, theta, x0, y0, s0, o, b0);
-    w.k = a;
-    w.batch = nb;
+  for (int64_t b0 = 0; b0 < batch && rc == MCPX_OK; b0 += wg::kChunk) {
+    w.batch = std::min(wg::kChunk, batch - b0);
     hipError_t e = hipMemsetAsync(w.counter, 0, sizeof(int32_t), st);
-    if (e == hipSuccess) {
-      if (mod) {
-        void* params[] = {&w};
-        e = hipModuleLaunchKernel(f, (unsigned)grid, 1, 1, mcpx::wg::kThreads, 1, 1, 0, st, params, nullptr);
-      } else {
-        e = mcpx::launch_ipm_wg(a.family, ls, nv, ns, w, grid, st);
-      }
-    }
-    if (e != hipSuccess) rc = fail(MCPX_EHIP, "workgroup solver launch failed: %s", hipGetErrorString(e));
+    if (e == hipSuccess) e = launch(b0, (int)std::min(grid_max, w.batch));
+    if (e != hipSuccess) rc = fail(MCPX_EHIP, "%s launch failed: %s", what, hipGetErrorString(e));
   }
-  dev_release(ws, st);
+  dev_release(w.work, st);
   return rc;
+}
+
+// Workgroup-per-instance solve (ipm_wg_impl.hpp): the slot holds [K | rhs] row-major, and
+// for a generated module its Jacobian blocks (wg_layout.h).
+int launch_wg(const mcpx_desc* d, const double* theta, const double* x0, const double* y0, const double* s0,
+              const mcpx_out* o, const mcpx::KernelArgs& a, const SolvePlan& plan, hipStream_t st) {
+  const int ls = a.solver, nv = plan.nmax, ns = wg::system_rows(ls, d->n, d->m);
+  GridKernel k;
+  if (plan.mod) {
+    const int rc = nl_function(plan.mod, ls, "_wg", &k.f);
+    if (rc) return rc;
+  } else {
+    k.sym = mcpx::ipm_wg_kernel(a.family, ls, nv, ns);
+    if (!k.sym) return fail(MCPX_EUNSUPPORTED, "no workgroup kernel for family %d, linear_solver %d, dim %d", a.family, ls, nv);
+  }
+  wg::WgArgs w = wg::solve_layout(ls, d->n, d->m, plan.mod ? plan.mod->meta[kMetaBlock] : 0);
+  return launch_persistent(k, -1, d->batch, w, 0, st, "workgroup solver", [&](int64_t b0, int grid) {
+    w.k = a;
+    set_chunk(w.k, d, theta, x0, y0, s0, o, b0);
+    return plan.mod ? launch_module(k.f, grid, k.threads, &w, st)
+                    : mcpx::launch_ipm_wg(a.family, ls, nv, ns, w, grid, st);
+  });
 }
 
 // The band SCHUR kernel of a generated module (ipm_nl_band.hpp): one wave per resident slot
-// on the work queue of the workgroup kernels, no workspace (LDS and VGPRs only).
+// on the work queue of the workgroup kernels; the slot is the kernel's own workspace (its U
+// rows when they exceed its VGPR budget, else none: LDS and VGPRs only).
 int launch_band(const mcpx_desc* d, const double* theta, const double* x0, const double* y0, const double* s0,
-                const mcpx_out* o, mcpx::KernelArgs a, hipStream_t st, mcpx_module* mod) {
+                const mcpx_out* o, const mcpx::KernelArgs& a, const SolvePlan& plan, hipStream_t st) {
+  GridKernel k;
+  k.threads = 64;
   int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  hipModule_t hm;
-  int rc = module_on(mod, dev, &hm);
+  const int rc = module_function(plan.mod, "mcpx_nl_solve_band", "band", &k.f, &dev);
   if (rc) return rc;
-  hipFunction_t f = nullptr;
-  if (hipModuleGetFunction(&f, hm, "mcpx_nl_solve_band") != hipSuccess)
-    return fail(MCPX_EUNSUPPORTED, "the generated module has no band kernel");
-  int per_cu = 0, cus = 0;
-  HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, 64, 0));
-  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const int64_t slots_max = (int64_t)std::max(per_cu, 1) * std::max(cus, 1);
-  // the kernel's per-slot HBM workspace (its U rows when they exceed its VGPR budget, mcpx_nl_meta[9])
-  const int64_t stride = ((int64_t)mod->meta[9] + 31) / 32 * 32;
-  const int64_t grid_max = std::min(slots_max, std::min((int64_t)1 << 30, d->batch));
-  double* ws = nullptr;
-  HIP_TRY(dev_alloc((void**)&ws, sizeof(double) * (size_t)(grid_max * stride) + 256, st));
-  int32_t* counter = (int32_t*)(ws + grid_max * stride);
-  mcpx::wg::WgArgs w{};
-  w.counter = counter;
-  w.work = ws;
-  w.slot_stride = stride;
-  const int64_t CH = (int64_t)1 << 30;
-  for (int64_t b0 = 0; b0 < d->batch && rc == MCPX_OK; b0 += CH) {
-    const int64_t nb = std::min(CH, d->batch - b0);
-    const int grid = (int)std::min(grid_max, nb);
-    set_chunk(a, d, theta, x0, y0, s0, o, b0);
+  wg::WgArgs w{};
+  w.slot_stride = wg::align(plan.mod->meta[kMetaBandWs]);
+  return launch_persistent(k, dev, d->batch, w, 0, st, "band solver", [&](int64_t b0, int grid) {
     w.k = a;
-    w.batch = nb;
-    hipError_t e = hipMemsetAsync(counter, 0, sizeof(int32_t), st);
-    if (e == hipSuccess) {
-      void* params[] = {&w};
-      e = hipModuleLaunchKernel(f, (unsigned)grid, 1, 1, 64, 1, 1, 0, st, params, nullptr);
-    }
-    if (e != hipSuccess) rc = fail(MCPX_EHIP, "band solver launch failed: %s", hipGetErrorString(e));
-  }
-  dev_release(ws, st);
-  return rc;
+    set_chunk(w.k, d, theta, x0, y0, s0, o, b0);
+    return launch_module(k.f, grid, k.threads, &w, st);
+  });
 }
 
 int launch_chunks(const mcpx_desc* d, const double* theta, const double* x0, const double* y0,
-                  const double* s0, const mcpx_out* o, mcpx::KernelArgs a, int nmax, hipStream_t st,
-                  mcpx_module* mod = nullptr, bool wg = false, bool mw = false, bool band = false) {
-  if (band) return launch_band(d, theta, x0, y0, s0, o, a, st, mod);
-  if (wg) return launch_wg(d, theta, x0, y0, s0, o, a, nmax, st, mod);
+                  const double* s0, const mcpx_out* o, mcpx::KernelArgs a, const SolvePlan& plan, hipStream_t st) {
+  if (plan.band) return launch_band(d, theta, x0, y0, s0, o, a, plan, st);
+  if (plan.wg) return launch_wg(d, theta, x0, y0, s0, o, a, plan, st);
   hipFunction_t nlf = nullptr;  // generated module: its kernel, launched by hipModuleLaunchKernel
-  if (mod) {
-    const int rc = nl_function(mod, a.solver, false, &nlf, mw);
+  if (plan.mod) {
+    const int rc = nl_function(plan.mod, a.solver, plan.mw ? "_mw" : "", &nlf);
     if (rc) return rc;
   }
-  const unsigned threads = mw ? 256 : 64;  // the multi-wave SCHUR kernel: 4 waves per instance
-  const int64_t CH = (int64_t)1 << 30;
-  for (int64_t b0 = 0; b0 < d->batch; b0 += CH) {
-    const int64_t nb = std::min(CH, d->batch - b0);
+  const unsigned threads = plan.mw ? 256 : 64;  // the multi-wave SCHUR kernel: 4 waves per instance
+  for (int64_t b0 = 0; b0 < d->batch; b0 += wg::kChunk) {
+    const int64_t nb = std::min(wg::kChunk, d->batch - b0);
     set_chunk(a, d, theta, x0, y0, s0, o, b0);
-    if (mod) {
-      void* params[] = {&a};
-      HIP_TRY(hipModuleLaunchKernel(nlf, (unsigned)nb, 1, 1, threads, 1, 1, 0, st, params, nullptr));
-    } else {
-      HIP_TRY(launch(nmax, a, nb, st));
-    }
+    if (plan.mod)
+      HIP_TRY(launch_module(nlf, nb, threads, &a, st));
+    else
+      HIP_TRY(launch(plan.nmax, a, nb, st));
   }
   return MCPX_OK;
 }
@@ -423,168 +435,8 @@ bool outputs_ok(const mcpx_out* o) {
          o->trace_len >= 0;
 }
 
-// Library-internal device buffers: a per-device cache of hipMalloc'd blocks, never unmapped.
-// A block goes back to the cache with an event recorded on the stream of its last use; the
-// next user (any stream of that device) takes it after a stream wait on that event, so reuse
-// stays stream-ordered without host synchronisation.  (HIP 7.2's stream-ordered pools —
-// hipMallocFromPoolAsync / hipFreeAsync, whose default VM heap remaps recycled memory — gave
-// wrong answers here: from the fourth back-to-back host call on, ~15 of 1,024 T = 10 games
-// every other call, with torch's bundled HIP 7.0 runtime or DEBUG_HIP_MEM_POOL_VMHEAP=0
-// never; tools/band_stress.py)  Idle blocks beyond kCacheKeep bytes per
-// device are freed once their last use has completed; the cache lives for the process (no
-// HIP calls during teardown).
-constexpr uint64_t kCacheKeep = 4ull << 30;
-
-// MCPX_POISON=1 (debug): every block handed out is filled with 0xFF bytes (NaN doubles) up to
-// the requested size, and the rest of the block (at least kCanary bytes) with the canary byte
-// 0xA5.  At release the tail is read back and checked: a write past the requested size is
-// reported on stderr ("MCPX_POISON canary") and counted (mcpx_debug_canary_violations), and a
-// kernel result that depended on workspace read before it was written turns NaN or changes.
-// Host synchronisation at every release: a diagnostic mode, not for timing.
-constexpr size_t kCanary = 4096;
-constexpr unsigned char kCanaryByte = 0xA5;
-std::atomic<int64_t> g_canary_bad{0};
-
-bool poison_on() {
-  static const bool on = [] {
-    const char* v = std::getenv("MCPX_POISON");
-    return v && std::atoi(v) == 1;
-  }();
-  return on;
-}
-
-struct Block {
-  void* p = nullptr;
-  size_t bytes = 0;
-  size_t req = 0;             // MCPX_POISON: the size requested by the current user
-  hipEvent_t last = nullptr;  // recorded after the block's last use
-  bool busy = false;
-};
-
-// MCPX_POISON: fill a block just handed out (stream-ordered)
-hipError_t poison_block(Block& b, size_t bytes, hipStream_t st) {
-  b.req = bytes;
-  hipError_t e = hipMemsetAsync(b.p, 0xFF, bytes, st);
-  if (e == hipSuccess) e = hipMemsetAsync((char*)b.p + bytes, kCanaryByte, b.bytes - bytes, st);
-  return e;
-}
-
-// MCPX_POISON: check a block's tail after its last use on `st` (host-synchronising)
-void check_canary(const Block& b, hipStream_t st) {
-  const size_t tail = b.bytes - b.req;
-  std::vector<unsigned char> h(tail);
-  if (hipMemcpyAsync(h.data(), (const char*)b.p + b.req, tail, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    std::fprintf(stderr, "MCPX_POISON canary: could not read back block %p\n", b.p);
-    g_canary_bad.fetch_add(1);
-    return;
-  }
-  for (size_t i = 0; i < tail; ++i)
-    if (h[i] != kCanaryByte) {
-      std::fprintf(stderr, "MCPX_POISON canary: block %p (%zu bytes requested, %zu held) overwritten at +%zu\n",
-                   b.p, b.req, b.bytes, b.req + i);
-      g_canary_bad.fetch_add(1);
-      return;
-    }
-}
-
-struct BlockCache {
-  std::mutex mu;
-  std::map<int, std::vector<Block>> dev;  // device → blocks
-};
-
-BlockCache& block_cache() {
-  static BlockCache* c = new BlockCache;  // never destroyed
-  return *c;
-}
-
-hipError_t dev_alloc(void** p, size_t bytes, hipStream_t st) {
-  *p = nullptr;
-  int d = 0;
-  hipError_t e = hipGetDevice(&d);
-  if (e != hipSuccess) return e;
-  const size_t need = std::max<size_t>(bytes, 1) + (poison_on() ? kCanary : 0);
-  const size_t want = (need + (2u << 20) - 1) / (2u << 20) * (2u << 20);  // 2 MiB granules
-  BlockCache& c = block_cache();
-  std::lock_guard<std::mutex> lock(c.mu);
-  auto& v = c.dev[d];
-  Block* best = nullptr;  // the smallest idle block that fits without wasting more than half of it
-  for (auto& b : v)
-    if (!b.busy && b.bytes >= want && b.bytes <= 2 * want && (!best || b.bytes < best->bytes)) best = &b;
-  if (best) {
-    if (best->last && (e = hipStreamWaitEvent(st, best->last, 0)) != hipSuccess) return e;
-    if (poison_on() && (e = poison_block(*best, bytes, st)) != hipSuccess) return e;
-    best->busy = true;
-    *p = best->p;
-    return hipSuccess;
-  }
-  Block b;
-  b.bytes = want;
-  if ((e = hipMalloc(&b.p, want)) != hipSuccess) {
-    // out of memory: free the idle blocks (after their last use) and try once more
-    for (auto it = v.begin(); it != v.end();) {
-      if (it->busy) { ++it; continue; }
-      if (it->last) (void)hipEventSynchronize(it->last), (void)hipEventDestroy(it->last);
-      (void)hipFree(it->p);
-      it = v.erase(it);
-    }
-    (void)hipGetLastError();
-    if ((e = hipMalloc(&b.p, want)) != hipSuccess) return e;
-  }
-  if (poison_on() && (e = poison_block(b, bytes, st)) != hipSuccess) return e;
-  b.busy = true;
-  v.push_back(b);
-  *p = b.p;
-  return hipSuccess;
-}
-
-void dev_release(void* p, hipStream_t st) {
-  if (!p) return;
-  BlockCache& c = block_cache();
-  std::lock_guard<std::mutex> lock(c.mu);
-  for (auto& [d, v] : c.dev) {
-    for (auto& b : v) {
-      if (b.p != p) continue;
-      if (poison_on()) check_canary(b, st);
-      if (!b.last) (void)hipEventCreateWithFlags(&b.last, hipEventDisableTiming);
-      if (b.last) (void)hipEventRecord(b.last, st);
-      b.busy = false;
-      uint64_t idle = 0;  // trim: idle bytes beyond kCacheKeep, oldest first, once completed
-      for (auto& q : v) idle += q.busy ? 0 : q.bytes;
-      for (auto it = v.begin(); it != v.end() && idle > kCacheKeep;) {
-        if (it->busy || it->p == p || (it->last && hipEventQuery(it->last) != hipSuccess)) { ++it; continue; }
-        idle -= it->bytes;
-        if (it->last) (void)hipEventDestroy(it->last);
-        (void)hipFree(it->p);
-        it = v.erase(it);
-      }
-      (void)d;
-      return;
-    }
-  }
-}
-
-template <class T>
-struct DevBuf {  // a cache block used on the null stream (synchronous callers)
-  T* p = nullptr;
-  ~DevBuf() { dev_release(p, nullptr); }
-  hipError_t alloc(size_t count) { return count ? dev_alloc((void**)&p, count * sizeof(T), nullptr) : hipSuccess; }
-};
-
-template <class T>
-struct AsyncBuf {  // a cache block, released on the stream it was allocated on
-  T* p = nullptr;
-  hipStream_t st = nullptr;
-  hipError_t alloc(size_t count, hipStream_t s) {
-    st = s;
-    return count ? dev_alloc((void**)&p, count * sizeof(T), s) : hipSuccess;
-  }
-  ~AsyncBuf() { dev_release(p, st); }
-};
-
 // θ buffers the host-buffer pipeline rotates through: MCPX_HOST_BUFFERS (A/B knob, 2..8,
 // default 3: chunk c+1 and c+2 upload while chunk c solves).
-constexpr int kMaxHostBufs = 8;
 int host_buffers() {
   const char* e = std::getenv("MCPX_HOST_BUFFERS");
   const int v = e ? std::atoi(e) : 3;
@@ -599,67 +451,6 @@ int64_t host_chunk() {
   return v < 1024 ? 1024 : v;
 }
 
-// The pipeline's two streams and per-buffer events.  Creating streams per call maps new
-// hardware queues every time (≈10 ms per call: profiles/r02/host_pipeline_trace.txt), so
-// they come from a process-wide free list per device: a call takes one Pipe and gives
-// it back when it returns, concurrent calls get different ones (the ABI stays
-// reentrant), and none is ever destroyed (no HIP calls during process teardown).
-struct Pipe {
-  hipStream_t up = nullptr, comp = nullptr;  // H→D uploads (serialised: full PCIe rate each), kernels
-  hipEvent_t copied[kMaxHostBufs] = {}, consumed[kMaxHostBufs] = {};
-  hipError_t init() {
-    hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&up, hipStreamNonBlocking)) != hipSuccess) return e;
-    if ((e = hipStreamCreateWithFlags(&comp, hipStreamNonBlocking)) != hipSuccess) return e;
-    for (int k = 0; k < kMaxHostBufs; ++k) {
-      if ((e = hipEventCreateWithFlags(&copied[k], hipEventDisableTiming)) != hipSuccess) return e;
-      if ((e = hipEventCreateWithFlags(&consumed[k], hipEventDisableTiming)) != hipSuccess) return e;
-    }
-    return hipSuccess;
-  }
-  void destroy() {  // a Pipe whose init() failed part-way: release what it created
-    for (int k = 0; k < kMaxHostBufs; ++k) {
-      if (copied[k]) (void)hipEventDestroy(copied[k]);
-      if (consumed[k]) (void)hipEventDestroy(consumed[k]);
-    }
-    if (up) (void)hipStreamDestroy(up);
-    if (comp) (void)hipStreamDestroy(comp);
-  }
-};
-
-std::mutex g_pipe_mu;
-std::map<int, std::vector<Pipe*>> g_pipe_free;
-
-struct PipeLease {  // a Pipe of device `dev` for the duration of one call (current device = dev)
-  Pipe* p = nullptr;
-  int dev = -1;
-  int acquire(int d) {
-    dev = d;
-    {
-      std::lock_guard<std::mutex> lock(g_pipe_mu);
-      auto& v = g_pipe_free[d];
-      if (!v.empty()) {
-        p = v.back();
-        v.pop_back();
-        return MCPX_OK;
-      }
-    }
-    Pipe* q = new Pipe;
-    if (hipError_t e = q->init(); e != hipSuccess) {
-      q->destroy();
-      delete q;
-      return fail(MCPX_EHIP, "stream setup: %s", hipGetErrorString(e));
-    }
-    p = q;
-    return MCPX_OK;
-  }
-  ~PipeLease() {
-    if (!p) return;
-    std::lock_guard<std::mutex> lock(g_pipe_mu);
-    g_pipe_free[dev].push_back(p);
-  }
-};
-
 // One device's share of mcpx_solve_batch: instances [b0, b0+nb), pipelined in chunks
 // of MCPX_HOST_CHUNK instances through NB rotating θ buffers.  θ (and warm starts) of
 // every chunk go up on ONE upload stream, back to back at the full host-link rate; the
@@ -667,19 +458,16 @@ struct PipeLease {  // a Pipe of device `dev` for the duration of one call (curr
 // c + NB waits for chunk c's kernel to release its buffer (event).  Outputs land in
 // whole-shard device buffers and come back once, after the last kernel.
 int solve_shard(int dev, const mcpx_desc* d, const double* theta, const double* x0, const double* y0,
-                const double* s0, const mcpx_params* prm, mcpx_out* o, int64_t b0, int64_t nb,
-                mcpx_module* mod = nullptr) {
+                const double* s0, const mcpx::KernelArgs& a, const SolvePlan& plan, mcpx_out* o, int64_t b0,
+                int64_t nb) {
   HIP_TRY(hipSetDevice(dev));
   int rc = check_device(dev);
   if (rc) return rc;
-  mcpx::KernelArgs a;
-  int nmax;
-  bool wg = false, mw = false, band = false;
-  if ((rc = prepare(d, prm, &a, &nmax, mod, &wg, &mw, &band))) return rc;
   const int n = d->n, m = d->m;
   const int64_t W = mask_words(m);
   PipeLease lease;
-  if ((rc = lease.acquire(dev))) return rc;
+  if (const hipError_t e = lease.acquire(dev); e != hipSuccess)
+    return fail(MCPX_EHIP, "stream setup: %s", hipGetErrorString(e));
   Pipe* P = lease.p;
   const int NB = host_buffers();
   const int64_t ch = std::min(host_chunk(), nb);
@@ -739,7 +527,7 @@ int solve_shard(int dev, const mcpx_desc* d, const double* theta, const double* 
     od.fail_reason = fr.p ? fr.p + c0 : nullptr;
     mcpx_desc dd = *d;
     dd.batch = cn;
-    if ((rc = launch_chunks(&dd, th[k].p, wx[k].p, wy[k].p, ws[k].p, &od, a, nmax, cs, mod, wg, mw, band))) return rc;
+    if ((rc = launch_chunks(&dd, th[k].p, wx[k].p, wy[k].p, ws[k].p, &od, a, plan, cs))) return rc;
     HIP_TRY(hipEventRecord(P->consumed[k], cs));
   }
   HIP_TRY(hipStreamSynchronize(us));
@@ -762,7 +550,50 @@ int solve_shard(int dev, const mcpx_desc* d, const double* theta, const double* 
 }
 
 
+// Shards of a host-buffer call: one per device, or MCPX_HOST_SHARDS = k contiguous shards
+// over the caller's (clamped) devices round-robin — shard g runs on device g mod
+// num_devices, never on a device the caller did not ask for (a test knob that runs the
+// multi-device path on a box with fewer devices).
+int host_shards(int num_devices, int64_t batch) {
+  const char* e = std::getenv("MCPX_HOST_SHARDS");
+  const int k = e ? std::atoi(e) : 0;
+  if (k <= 0) return num_devices;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(k, batch));
+}
+
+// Runs fn(device, b0, nb) over the contiguous shards of a host-buffer call: shard g (device
+// g mod devices) gets ⌊B/G⌋ instances (+1 for g < B mod G).  One host thread per shard; a
+// single shard runs on the caller's thread.
+template <class Fn>
+int run_shards(int num_devices, int64_t batch, Fn&& fn) {
+  const int avail = mcpx_device_count();
+  if (avail < 1) return fail(MCPX_ENODEV, "no HIP device visible");
+  if (num_devices <= 0 || num_devices > avail) num_devices = avail;
+  if ((int64_t)num_devices > batch) num_devices = (int)batch;
+  const int devs = num_devices, shards = host_shards(devs, batch);
+  if (shards == 1) return fn(0, (int64_t)0, batch);
+  std::vector<int64_t> start(shards + 1, 0);
+  for (int g = 0; g < shards; ++g) start[g + 1] = start[g] + batch / shards + (g < batch % shards ? 1 : 0);
+  std::vector<int> rcs(shards, 0);
+  std::vector<std::string> errs(shards);
+  std::vector<std::thread> th;
+  for (int g = 0; g < shards; ++g)
+    th.emplace_back([&, g] {
+      rcs[g] = fn(g % devs, start[g], start[g + 1] - start[g]);
+      if (rcs[g]) errs[g] = g_err;
+    });
+  for (auto& t : th) t.join();
+  for (int g = 0; g < shards; ++g)
+    if (rcs[g]) return fail(rcs[g], "device %d: %s", g, errs[g].c_str());
+  return MCPX_OK;
+}
+
 // ---- sensitivities (src/AutoDiff.jl) ----------------------------------------
+
+// mcpx_vjp_batch*, mcpx_jvp_batch*, or mcpx_cond_batch*: the JVP workgroup kernels in their
+// condition-estimate mode (every size and family runs the workgroup layout: the estimate's
+// solves reuse the factors in the slot).
+enum SensKind { kVjp, kJvp, kCond };
 
 // How a sensitivity call runs: one wave per instance (QP / affine, n + 2m ≤ 64: the
 // register kernels of sens_kernel_impl.hpp, `nmax` wide) or one workgroup per instance
@@ -774,182 +605,114 @@ struct SensPlan {
   mcpx_module* mod = nullptr;
 };
 
-// Validates a sensitivity call; fills the scalar part of the args and the plan.
-int prepare_sens(const mcpx_desc* d, mcpx::SensArgs* a, SensPlan* plan, bool jvp, mcpx_module* mod = nullptr) {
+// Validates a sensitivity call; fills the scalar part of the args (the caller's pointers,
+// n_partials and cotangent factors stay) and the plan.
+int prepare_sens(const mcpx_desc* d, mcpx::SensArgs* a, SensPlan* plan, SensKind kind, mcpx_module* mod) {
   if (!d) return fail(MCPX_EINVAL, "desc must be non-NULL");
   int64_t pd;
-  if (mod) {
-    if (d->family != MCPX_FAMILY_NONLINEAR)
-      return fail(MCPX_EINVAL, "a generated module differentiates family MCPX_FAMILY_NONLINEAR (got %d)", d->family);
-    if (d->n != mod->meta[1] || d->m != mod->meta[2])
-      return fail(MCPX_EINVAL, "desc (n=%d, m=%d) does not match the module (n=%d, m=%d)", d->n, d->m,
-                  mod->meta[1], mod->meta[2]);
-    pd = mod->meta[3];
-  } else {
-    if (d->family == MCPX_FAMILY_NONLINEAR)
-      return fail(MCPX_EINVAL, "family MCPX_FAMILY_NONLINEAR is differentiated through its generated module "
-                  "(mcpx_vjp_batch_module / mcpx_jvp_batch_module)");
-    pd = mcpx_theta_dim(d->family, d->n, d->m);
-  }
-  if (pd < 0) return fail(MCPX_EINVAL, "bad family %d or negative dimensions (n=%d, m=%d)", d->family, d->n, d->m);
-  if (d->n + d->m < 1) return fail(MCPX_EINVAL, "empty problem (n = m = 0)");
-  if (d->batch < 0) return fail(MCPX_EINVAL, "negative batch");
-  if (d->theta_ld < pd) return fail(MCPX_EINVAL, "theta_ld %lld < parameter dimension %lld", (long long)d->theta_ld, (long long)pd);
+  if (const int rc = check_desc(d, mod, &pd, kSensWords)) return rc;
+  const bool jvp = kind != kVjp;
   const int N = d->n + 2 * d->m;
   *plan = SensPlan{};
   plan->mod = mod;
   if (mod) {
-    const int bit = jvp ? MCPX_MODULE_JVP : MCPX_MODULE_VJP;
-    if (!((mod->meta[5] >> bit) & 1))
+    if (!mod->has(jvp ? MCPX_MODULE_JVP : MCPX_MODULE_VJP))
       return fail(MCPX_EUNSUPPORTED, "the generated module has no %s kernel (n=%d m=%d: not even a 4-column LU panel of "
                   "its %d-row system fits the LDS)", jvp ? "JVP" : "VJP", d->n, d->m, jvp ? N : d->n + d->m);
     plan->wg = true;
-  } else if (N <= MCPX_MAX_KKT_DIM) {
-    plan->nmax = pick_nmax(N);
   } else if (N <= MCPX_MAX_WG_KKT_DIM) {
-    plan->wg = true;
-    plan->nv = pick_wg_bucket(N);
+    if (N <= MCPX_MAX_KKT_DIM && kind != kCond) {
+      plan->nmax = pick_nmax(N);
+    } else {
+      plan->wg = true;
+      plan->nv = pick_wg_bucket(N);
+    }
   } else {
     return fail(MCPX_EUNSUPPORTED, "sensitivities need n + 2m <= %d (got n=%d m=%d)", MCPX_MAX_WG_KKT_DIM, d->n, d->m);
   }
-  std::memset(a, 0, sizeof *a);
   a->theta_ld = d->theta_ld;
   a->p = pd;
   a->n = d->n;
   a->m = d->m;
   a->family = d->family;
+  a->mode = kind == kCond ? 1 : 0;
   return MCPX_OK;
 }
 
-// Workgroup-per-instance sensitivity launch (sens_wg_impl.hpp): persistent grid of the
-// resident workgroups on an atomic work queue, per-slot HBM workspace for [K | rhs]
-// (and a module's Jacobian blocks and ∇F_θ), allocated stream-ordered for this call.
-int launch_sens_wg_impl(bool jvp, const mcpx_desc* d, mcpx::SensArgs a, const SensPlan& plan, hipStream_t st) {
-  const int n = d->n, m = d->m, N = n + 2 * m, nr = n + m;
-  const int ns = jvp ? N : nr;
-  const int K = a.n_partials;
-  // (the condition estimate: two N-vectors of scratch in the right-hand-side area)
-  const int nrhs = a.mode == 1 ? 2 : (jvp ? std::max(1, std::min(K, MCPX_JVP_RHS)) : 1);
-  hipFunction_t f = nullptr;
-  const void* kp = nullptr;
-  int per_cu = 0;
+// The argument checks after prepare_sens; an empty batch reads nothing and passes.
+int sens_inputs_ok(const mcpx_desc* d, const mcpx::SensArgs& a) {
+  if (a.n_partials < 0) return fail(MCPX_EINVAL, "negative n_partials");
+  if (d->batch == 0) return MCPX_OK;
+  if (!a.theta || !a.out) return fail(MCPX_EINVAL, "theta and the output array must be non-NULL");
+  if ((d->n > 0 && !a.x) || (d->m > 0 && (!a.y || !a.s)))
+    return fail(MCPX_EINVAL, "solution arrays x/y/s must be non-NULL");
+  if (a.n_partials > 0 && !a.theta_dot) return fail(MCPX_EINVAL, "theta_dot is NULL");
+  return MCPX_OK;
+}
+
+// Doubles of one instance's output: rcond, zdot [K × (n+2m)] or dtheta [p].
+int64_t sens_out_len(const mcpx::SensArgs& a, bool jvp) {
+  return a.mode == 1 ? 1 : (jvp ? (int64_t)a.n_partials * (a.n + 2 * a.m) : a.p);
+}
+
+// The args of the chunk that starts at instance b0 (the counterpart of set_chunk).
+mcpx::SensArgs sens_chunk(mcpx::SensArgs a, bool jvp, int64_t b0) {
+  const int n = a.n, m = a.m;
+  a.out += b0 * sens_out_len(a, jvp);
+  a.theta += b0 * a.theta_ld;
+  a.x += b0 * n;
+  a.y += b0 * m;
+  a.s += b0 * m;
+  if (a.gx) a.gx += b0 * n;
+  if (a.gy) a.gy += b0 * m;
+  if (a.gs) a.gs += b0 * m;
+  if (a.theta_dot) a.theta_dot += b0 * a.n_partials * a.p;
+  if (a.status) a.status += b0;
+  return a;
+}
+
+// Workgroup-per-instance sensitivity launch (sens_wg_impl.hpp): the slot holds [K | rhs]
+// (and a module's Jacobian blocks and ∇F_θ, wg_layout.h).
+int launch_sens_wg_impl(bool jvp, const mcpx_desc* d, const mcpx::SensArgs& a, const SensPlan& plan, hipStream_t st) {
+  GridKernel k;
   if (plan.mod) {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    hipModule_t hm;
-    const int rc = module_on(plan.mod, dev, &hm);
-    if (rc) return rc;
     const char* name = jvp ? "mcpx_nl_jvp_wg" : "mcpx_nl_vjp_wg";
-    if (hipModuleGetFunction(&f, hm, name) != hipSuccess)
-      return fail(MCPX_EUNSUPPORTED, "the generated module has no %s kernel", name);
-    HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, mcpx::wg::kThreads, 0));
+    int dev = 0;
+    const int rc = module_function(plan.mod, name, name, &k.f, &dev);
+    if (rc) return rc;
   } else {
-    kp = mcpx::sens_wg_kernel(a.family, jvp, plan.nv);
-    if (!kp) return fail(MCPX_EUNSUPPORTED, "no workgroup sensitivity kernel for family %d, dim %d", a.family, plan.nv);
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, mcpx::wg::kThreads, 0));
+    k.sym = mcpx::sens_wg_kernel(a.family, jvp, plan.nv);
+    if (!k.sym) return fail(MCPX_EUNSUPPORTED, "no workgroup sensitivity kernel for family %d, dim %d", a.family, plan.nv);
   }
-  int dev = 0, cus = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const int64_t slots_max = (int64_t)std::max(per_cu, 1) * std::max(cus, 1);
-  auto align = [](int64_t v) { return (v + 31) / 32 * 32; };  // 256-B boundaries
-  mcpx::wg::WgSensArgs w{};
-  w.ld = ns + nrhs;
-  w.nrhs = nrhs;
-  w.off_blk = align((int64_t)ns * w.ld);
-  w.off_dth = align(w.off_blk + (plan.mod ? plan.mod->meta[6] : 0));
-  w.off_sol = align(w.off_dth + (plan.mod ? (int64_t)nr * a.p : 0));
-  w.slot_stride = align(w.off_sol + (jvp ? (int64_t)nrhs * ns : 0));
-  const int64_t CH = (int64_t)1 << 30;
-  int64_t grid_max = std::min(slots_max, std::min(CH, d->batch));
-  // a long-horizon module's slot is tens of MB (T = 30 tangents: 35 MB of [K | rhs] alone): the
-  // persistent grid takes at most 4 GiB of workspace, fewer workgroups on the same queue
-  const int64_t ws_cap = ((int64_t)4 << 30) / (int64_t)sizeof(double);
-  if (grid_max * w.slot_stride > ws_cap) grid_max = std::max<int64_t>(1, ws_cap / w.slot_stride);
-  double* ws = nullptr;
-  const size_t bytes = sizeof(double) * (size_t)(grid_max * w.slot_stride) + 256;
-  HIP_TRY(dev_alloc((void**)&ws, bytes, st));
-  w.work = ws;
-  w.counter = (int32_t*)(ws + grid_max * w.slot_stride);
-  int rc = MCPX_OK;
-  for (int64_t b0 = 0; b0 < d->batch && rc == MCPX_OK; b0 += CH) {
-    const int64_t nb = std::min(CH, d->batch - b0);
-    const int grid = (int)std::min(grid_max, nb);
-    w.s = a;
-    w.s.theta = a.theta + b0 * d->theta_ld;
-    w.s.x = a.x + b0 * n;
-    w.s.y = a.y + b0 * m;
-    w.s.s = a.s + b0 * m;
-    w.s.gx = a.gx ? a.gx + b0 * n : nullptr;
-    w.s.gy = a.gy ? a.gy + b0 * m : nullptr;
-    w.s.gs = a.gs ? a.gs + b0 * m : nullptr;
-    w.s.theta_dot = a.theta_dot ? a.theta_dot + b0 * K * a.p : nullptr;
-    w.s.out = a.out + (a.mode == 1 ? b0 : (jvp ? b0 * K * N : b0 * a.p));
-    w.s.status = a.status ? a.status + b0 : nullptr;
-    w.batch = nb;
-    hipError_t e = hipMemsetAsync(w.counter, 0, sizeof(int32_t), st);
-    if (e == hipSuccess) {
-      if (plan.mod) {
-        void* params[] = {&w};
-        e = hipModuleLaunchKernel(f, (unsigned)grid, 1, 1, mcpx::wg::kThreads, 1, 1, 0, st, params, nullptr);
-      } else {
-        e = mcpx::launch_sens_wg(a.family, jvp, plan.nv, w, grid, st);
-      }
-    }
-    if (e != hipSuccess) rc = fail(MCPX_EHIP, "workgroup sensitivity launch failed: %s", hipGetErrorString(e));
-  }
-  dev_release(ws, st);
-  return rc;
+  wg::WgSensArgs w = wg::sens_layout(jvp, a.mode, a.n, a.m, a.p, a.n_partials,
+                                     plan.mod ? plan.mod->meta[kMetaBlock] : wg::kNoModule);
+  return launch_persistent(k, -1, d->batch, w, wg::kSensWorkCap, st, "workgroup sensitivity", [&](int64_t b0, int grid) {
+    w.s = sens_chunk(a, jvp, b0);
+    return plan.mod ? launch_module(k.f, grid, k.threads, &w, st)
+                    : mcpx::launch_sens_wg(a.family, jvp, plan.nv, w, grid, st);
+  });
 }
 
 // Enqueue VJP (jvp = false) or JVP launches over the batch: the one-wave kernels in
 // chunks of 2^30 instances, or the workgroup kernels.
-int launch_sens(bool jvp, const mcpx_desc* d, mcpx::SensArgs a, const SensPlan& plan, const double* theta,
-                const double* x, const double* y, const double* s, const double* gx, const double* gy,
-                const double* gs, const double* tdot, double* out, int32_t* status, hipStream_t st) {
-  if (plan.wg) {
-    a.theta = theta;
-    a.x = x;
-    a.y = y;
-    a.s = s;
-    a.gx = gx;
-    a.gy = gy;
-    a.gs = gs;
-    a.theta_dot = tdot;
-    a.out = out;
-    a.status = status;
-    return launch_sens_wg_impl(jvp, d, a, plan, st);
-  }
-  const int64_t CH = (int64_t)1 << 30;
-  const int n = d->n, m = d->m, N = n + 2 * m, K = a.n_partials;
-  for (int64_t b0 = 0; b0 < d->batch; b0 += CH) {
-    const int64_t nb = std::min(CH, d->batch - b0);
-    a.theta = theta + b0 * d->theta_ld;
-    a.x = x + b0 * n;
-    a.y = y + b0 * m;
-    a.s = s + b0 * m;
-    a.gx = gx ? gx + b0 * n : nullptr;
-    a.gy = gy ? gy + b0 * m : nullptr;
-    a.gs = gs ? gs + b0 * m : nullptr;
-    a.theta_dot = tdot ? tdot + b0 * K * a.p : nullptr;
-    a.out = out + (jvp ? b0 * K * N : b0 * a.p);
-    a.status = status ? status + b0 : nullptr;
+int launch_sens(bool jvp, const mcpx_desc* d, const mcpx::SensArgs& a, const SensPlan& plan, hipStream_t st) {
+  if (plan.wg) return launch_sens_wg_impl(jvp, d, a, plan, st);
+  for (int64_t b0 = 0; b0 < d->batch; b0 += wg::kChunk) {
+    const int64_t nb = std::min(wg::kChunk, d->batch - b0);
+    const mcpx::SensArgs c = sens_chunk(a, jvp, b0);
     // the VJP factors the slack-eliminated (n+m)-dim system, the JVP the full n+2m
-    HIP_TRY(jvp ? mcpx::launch_jvp(plan.nmax, a, nb, st) : mcpx::launch_vjp(pick_nmax(n + m), a, nb, st));
+    HIP_TRY(jvp ? mcpx::launch_jvp(plan.nmax, c, nb, st) : mcpx::launch_vjp(pick_nmax(a.n + a.m), c, nb, st));
   }
   return MCPX_OK;
 }
 
-// One device's share [b0, b0+nb) of a host-buffer sensitivity call.
-int sens_shard(bool jvp, int dev, const mcpx_desc* d, const mcpx::SensArgs& a0, const SensPlan& plan,
-               const double* theta, const double* x, const double* y, const double* s, const double* gx,
-               const double* gy, const double* gs, const double* tdot, double* out, int32_t* status, int64_t b0,
+// One device's share [b0, b0+nb) of a host-buffer sensitivity call (`a`: host pointers).
+int sens_shard(bool jvp, int dev, const mcpx_desc* d, const mcpx::SensArgs& a, const SensPlan& plan, int64_t b0,
                int64_t nb) {
   HIP_TRY(hipSetDevice(dev));
   int rc = check_device(dev);
   if (rc) return rc;
-  const int n = d->n, m = d->m, N = n + 2 * m, K = a0.n_partials;
-  const int64_t p = a0.p;
+  const int n = d->n, m = d->m;
   DevBuf<double> th, dx, dy, ds, dgx, dgy, dgs, dtd, dout;
   DevBuf<int32_t> dst;
   auto up = [&](DevBuf<double>& b, const double* h, size_t per) -> hipError_t {
@@ -957,176 +720,76 @@ int sens_shard(bool jvp, int dev, const mcpx_desc* d, const mcpx::SensArgs& a0, 
     hipError_t e = b.alloc((size_t)nb * per);
     return e != hipSuccess ? e : hipMemcpy(b.p, h + b0 * per, sizeof(double) * nb * per, hipMemcpyHostToDevice);
   };
-  HIP_TRY(up(th, theta, (size_t)d->theta_ld));
-  HIP_TRY(up(dx, x, n)); HIP_TRY(up(dy, y, m)); HIP_TRY(up(ds, s, m));
-  HIP_TRY(up(dgx, gx, n)); HIP_TRY(up(dgy, gy, m)); HIP_TRY(up(dgs, gs, m));
-  HIP_TRY(up(dtd, tdot, (size_t)K * p));
-  const size_t per_out = a0.mode == 1 ? 1 : (jvp ? (size_t)K * N : (size_t)p);
+  HIP_TRY(up(th, a.theta, (size_t)d->theta_ld));
+  HIP_TRY(up(dx, a.x, n)); HIP_TRY(up(dy, a.y, m)); HIP_TRY(up(ds, a.s, m));
+  HIP_TRY(up(dgx, a.gx, n)); HIP_TRY(up(dgy, a.gy, m)); HIP_TRY(up(dgs, a.gs, m));
+  HIP_TRY(up(dtd, a.theta_dot, (size_t)a.n_partials * a.p));
+  const size_t per_out = (size_t)sens_out_len(a, jvp);
   HIP_TRY(dout.alloc((size_t)nb * per_out));
-  if (status) HIP_TRY(dst.alloc(nb));
+  if (a.status) HIP_TRY(dst.alloc(nb));
   mcpx_desc dd = *d;
   dd.batch = nb;
+  mcpx::SensArgs da = a;  // the same call on the shard's device buffers
+  da.theta = th.p;
   // empty x/y blocks (n = 0 or m = 0) still need a valid base pointer
-  const double* bx = dx.p ? dx.p : th.p;
-  const double* by = dy.p ? dy.p : th.p;
-  const double* bs = ds.p ? ds.p : th.p;
+  da.x = dx.p ? dx.p : th.p;
+  da.y = dy.p ? dy.p : th.p;
+  da.s = ds.p ? ds.p : th.p;
+  da.gx = dgx.p;
+  da.gy = dgy.p;
+  da.gs = dgs.p;
+  da.theta_dot = dtd.p;
   // an empty output (p = 0, or K = 0) still needs a valid base pointer
-  double* bo = dout.p ? dout.p : (double*)th.p;
-  if ((rc = launch_sens(jvp, &dd, a0, plan, th.p, bx, by, bs, gx ? dgx.p : nullptr, gy ? dgy.p : nullptr,
-                        gs ? dgs.p : nullptr, dtd.p, bo, status ? dst.p : nullptr, nullptr))) {
+  da.out = dout.p ? dout.p : (double*)th.p;
+  da.status = dst.p;
+  if ((rc = launch_sens(jvp, &dd, da, plan, nullptr))) {
     (void)hipDeviceSynchronize();  // nothing may still run on the buffers freed on return
     return rc;
   }
   HIP_TRY(hipDeviceSynchronize());
-  if (per_out) HIP_TRY(hipMemcpy(out + b0 * per_out, dout.p, sizeof(double) * nb * per_out, hipMemcpyDeviceToHost));
-  if (status) HIP_TRY(hipMemcpy(status + b0, dst.p, sizeof(int32_t) * nb, hipMemcpyDeviceToHost));
+  if (per_out) HIP_TRY(hipMemcpy(a.out + b0 * per_out, dout.p, sizeof(double) * nb * per_out, hipMemcpyDeviceToHost));
+  if (a.status) HIP_TRY(hipMemcpy(a.status + b0, dst.p, sizeof(int32_t) * nb, hipMemcpyDeviceToHost));
   return MCPX_OK;
 }
 
-// Shards of a host-buffer call: one per device, or MCPX_HOST_SHARDS = k contiguous shards
-// over the caller's (clamped) devices round-robin — shard g runs on device g mod
-// num_devices, never on a device the caller did not ask for (one host thread each; a test
-// knob that runs the multi-device path on a box with fewer devices).
-int host_shards(int num_devices, int64_t batch) {
-  const char* e = std::getenv("MCPX_HOST_SHARDS");
-  const int k = e ? std::atoi(e) : 0;
-  if (k <= 0) return num_devices;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(k, batch));
-}
-
-// Host-buffer entry shared by mcpx_vjp_batch / mcpx_jvp_batch (and the module variants):
-// contiguous shards, one thread per device.
-int sens_host(bool jvp, const mcpx_desc* d, const mcpx::SensArgs& a, const SensPlan& plan, const double* theta,
-              const double* x, const double* y, const double* s, const double* gx, const double* gy,
-              const double* gs, const double* tdot, int num_devices, double* out, int32_t* status) {
-  const int avail = mcpx_device_count();
-  if (avail < 1) return fail(MCPX_ENODEV, "no HIP device visible");
-  if (num_devices <= 0 || num_devices > avail) num_devices = avail;
-  if ((int64_t)num_devices > d->batch) num_devices = (int)d->batch;
-  const int devs = num_devices;
-  num_devices = host_shards(devs, d->batch);
-  std::vector<int64_t> start(num_devices + 1, 0);
-  for (int g = 0; g < num_devices; ++g)
-    start[g + 1] = start[g] + d->batch / num_devices + (g < d->batch % num_devices ? 1 : 0);
-  std::vector<int> rcs(num_devices, 0);
-  std::vector<std::string> errs(num_devices);
-  std::vector<std::thread> th;
-  for (int g = 0; g < num_devices; ++g)
-    th.emplace_back([&, g] {
-      rcs[g] = sens_shard(jvp, g % devs, d, a, plan, theta, x, y, s, gx, gy, gs, tdot, out, status, start[g],
-                          start[g + 1] - start[g]);
-      if (rcs[g]) errs[g] = g_err;
-    });
-  for (auto& t : th) t.join();
-  for (int g = 0; g < num_devices; ++g)
-    if (rcs[g]) return fail(rcs[g], "device %d: %s", g, errs[g].c_str());
-  return MCPX_OK;
-}
-
-int sens_inputs_ok(const mcpx_desc* d, const double* theta, const double* x, const double* y, const double* s,
-                   const double* out) {
-  if (!theta || !out) return fail(MCPX_EINVAL, "theta and the output array must be non-NULL");
-  if ((d->n > 0 && !x) || (d->m > 0 && (!y || !s))) return fail(MCPX_EINVAL, "solution arrays x/y/s must be non-NULL");
-  return MCPX_OK;
-}
-
-int vjp_device_impl(mcpx_module* mod, const mcpx_desc* d, const double* theta, const double* x, const double* y,
-                    const double* s, const double* gx, const double* gy, const double* gs, double* dtheta,
-                    int32_t* status, void* stream) {
-  mcpx::SensArgs a;
+// The device-buffer sensitivity entries (`a`: the caller's pointers, n_partials): enqueued
+// on `stream` of the current device.
+int sens_device(SensKind kind, mcpx_module* mod, const mcpx_desc* d, mcpx::SensArgs a, void* stream) {
   SensPlan plan;
   int rc;
-  if ((rc = prepare_sens(d, &a, &plan, false, mod))) return rc;
-  if (d->batch == 0) return MCPX_OK;
-  if ((rc = sens_inputs_ok(d, theta, x, y, s, dtheta))) return rc;
+  if ((rc = prepare_sens(d, &a, &plan, kind, mod))) return rc;
+  if ((rc = sens_inputs_ok(d, a)) || d->batch == 0) return rc;
   int dev = 0;
   if ((rc = current_device(&dev))) return rc;
-  return launch_sens(false, d, a, plan, theta, x ? x : theta, y ? y : theta, s ? s : theta, gx, gy, gs, nullptr,
-                     dtheta, status, (hipStream_t)stream);
+  // empty x/y blocks (n = 0 or m = 0) still need a valid base pointer
+  if (!a.x) a.x = a.theta;
+  if (!a.y) a.y = a.theta;
+  if (!a.s) a.s = a.theta;
+  return launch_sens(kind != kVjp, d, a, plan, (hipStream_t)stream);
 }
 
-int vjp_host_impl(mcpx_module* mod, const mcpx_desc* d, const double* theta, const double* x, const double* y,
-                  const double* s, const double* gx, const double* gy, const double* gs, int num_devices,
-                  double* dtheta, int32_t* status) {
-  mcpx::SensArgs a;
+// The host-buffer sensitivity entries: contiguous shards over the devices.
+int sens_host(SensKind kind, mcpx_module* mod, const mcpx_desc* d, mcpx::SensArgs a, int num_devices) {
   SensPlan plan;
   int rc;
-  if ((rc = prepare_sens(d, &a, &plan, false, mod))) return rc;
-  if (d->batch == 0) return MCPX_OK;
-  if ((rc = sens_inputs_ok(d, theta, x, y, s, dtheta))) return rc;
-  return sens_host(false, d, a, plan, theta, x, y, s, gx, gy, gs, nullptr, num_devices, dtheta, status);
+  if ((rc = prepare_sens(d, &a, &plan, kind, mod))) return rc;
+  if ((rc = sens_inputs_ok(d, a)) || d->batch == 0) return rc;
+  return run_shards(num_devices, d->batch, [&](int dev, int64_t b0, int64_t nb) {
+    return sens_shard(kind != kVjp, dev, d, a, plan, b0, nb);
+  });
 }
 
-int jvp_device_impl(mcpx_module* mod, const mcpx_desc* d, const double* theta, const double* x, const double* y,
-                    const double* s, int32_t n_partials, const double* theta_dot, double* zdot, int32_t* status,
-                    void* stream) {
-  mcpx::SensArgs a;
-  SensPlan plan;
-  int rc;
-  if ((rc = prepare_sens(d, &a, &plan, true, mod))) return rc;
-  if (n_partials < 0) return fail(MCPX_EINVAL, "negative n_partials");
-  a.n_partials = n_partials;
-  if (d->batch == 0) return MCPX_OK;
-  if ((rc = sens_inputs_ok(d, theta, x, y, s, zdot))) return rc;
-  if (n_partials > 0 && !theta_dot) return fail(MCPX_EINVAL, "theta_dot is NULL");
-  int dev = 0;
-  if ((rc = current_device(&dev))) return rc;
-  return launch_sens(true, d, a, plan, theta, x ? x : theta, y ? y : theta, s ? s : theta, nullptr, nullptr,
-                     nullptr, theta_dot, zdot, status, (hipStream_t)stream);
-}
-
-int jvp_host_impl(mcpx_module* mod, const mcpx_desc* d, const double* theta, const double* x, const double* y,
-                  const double* s, int32_t n_partials, const double* theta_dot, int num_devices, double* zdot,
-                  int32_t* status) {
-  mcpx::SensArgs a;
-  SensPlan plan;
-  int rc;
-  if ((rc = prepare_sens(d, &a, &plan, true, mod))) return rc;
-  if (n_partials < 0) return fail(MCPX_EINVAL, "negative n_partials");
-  a.n_partials = n_partials;
-  if (d->batch == 0) return MCPX_OK;
-  if ((rc = sens_inputs_ok(d, theta, x, y, s, zdot))) return rc;
-  if (n_partials > 0 && !theta_dot) return fail(MCPX_EINVAL, "theta_dot is NULL");
-  return sens_host(true, d, a, plan, theta, x, y, s, nullptr, nullptr, nullptr, theta_dot, num_devices, zdot,
-                   status);
-}
-
-// mcpx_cond_batch*: the JVP workgroup kernels in their condition-estimate mode (every size and
-// family runs the workgroup layout: the estimate's solves reuse the factors in the slot).
-int prepare_cond(const mcpx_desc* d, mcpx::SensArgs* a, SensPlan* plan, mcpx_module* mod) {
-  int rc = prepare_sens(d, a, plan, true, mod);
-  if (rc) return rc;
-  if (!plan->wg) {
-    plan->wg = true;
-    plan->nv = pick_wg_bucket(d->n + 2 * d->m);
-  }
-  a->mode = 1;
-  return MCPX_OK;
-}
-
-int cond_device_impl(mcpx_module* mod, const mcpx_desc* d, const double* theta, const double* x, const double* y,
-                     const double* s, double* rcond, int32_t* status, void* stream) {
-  mcpx::SensArgs a;
-  SensPlan plan;
-  int rc;
-  if ((rc = prepare_cond(d, &a, &plan, mod))) return rc;
-  if (d->batch == 0) return MCPX_OK;
-  if ((rc = sens_inputs_ok(d, theta, x, y, s, rcond))) return rc;
-  int dev = 0;
-  if ((rc = current_device(&dev))) return rc;
-  return launch_sens(true, d, a, plan, theta, x ? x : theta, y ? y : theta, s ? s : theta, nullptr, nullptr,
-                     nullptr, nullptr, rcond, status, (hipStream_t)stream);
-}
-
-int cond_host_impl(mcpx_module* mod, const mcpx_desc* d, const double* theta, const double* x, const double* y,
-                   const double* s, int num_devices, double* rcond, int32_t* status) {
-  mcpx::SensArgs a;
-  SensPlan plan;
-  int rc;
-  if ((rc = prepare_cond(d, &a, &plan, mod))) return rc;
-  if (d->batch == 0) return MCPX_OK;
-  if ((rc = sens_inputs_ok(d, theta, x, y, s, rcond))) return rc;
-  return sens_host(true, d, a, plan, theta, x, y, s, nullptr, nullptr, nullptr, nullptr, num_devices, rcond, status);
+// The pointer part of a sensitivity call's args, as the extern "C" entries receive it.
+mcpx::SensArgs sens_args(const double* theta, const double* x, const double* y, const double* s, double* out,
+                         int32_t* status) {
+  mcpx::SensArgs a{};
+  a.theta = theta;
+  a.x = x;
+  a.y = y;
+  a.s = s;
+  a.out = out;
+  a.status = status;
+  return a;
 }
 
 // mcpx_solve_batch_device / mcpx_solve_batch_module_device (mod = nullptr: QP / affine kernels).
@@ -1134,16 +797,15 @@ int solve_device_impl(mcpx_module* mod, const mcpx_desc* d, const double* theta,
                       const double* y0, const double* s0, const mcpx_params* prm, const mcpx_out* o,
                       void* stream) {
   mcpx::KernelArgs a;
-  int nmax;
-  bool wg = false, mw = false, band = false;
-  int rc = prepare(d, prm, &a, &nmax, mod, &wg, &mw, &band);
+  SolvePlan plan;
+  int rc = prepare(d, prm, &a, &plan, mod);
   if (rc) return rc;
   if (!outputs_ok(o)) return fail(MCPX_EINVAL, "required output arrays missing");
   if (d->batch == 0) return MCPX_OK;
   if (!theta) return fail(MCPX_EINVAL, "theta is NULL");
   int dev = 0;
   if ((rc = current_device(&dev))) return rc;
-  return launch_chunks(d, theta, x0, y0, s0, o, a, nmax, (hipStream_t)stream, mod, wg, mw, band);
+  return launch_chunks(d, theta, x0, y0, s0, o, a, plan, (hipStream_t)stream);
 }
 
 // mcpx_solve_vjp_batch_device: the solve kernels with the pullback in their epilogue
@@ -1152,13 +814,12 @@ int solve_vjp_device_impl(const mcpx_desc* d, const double* theta, const double*
                           const double* s0, const mcpx_params* prm, const mcpx_out* o, const mcpx_cotangent* ct,
                           double* dtheta, int32_t* vstat, void* stream) {
   mcpx::KernelArgs a;
-  int nmax;
-  bool wg = false;
-  int rc = prepare(d, prm, &a, &nmax, nullptr, &wg);
+  SolvePlan plan;
+  int rc = prepare(d, prm, &a, &plan, nullptr);
   if (rc) return rc;
-  mcpx::SensArgs sa;
-  SensPlan plan;
-  if ((rc = prepare_sens(d, &sa, &plan, false))) return rc;
+  mcpx::SensArgs sa{};
+  SensPlan splan;
+  if ((rc = prepare_sens(d, &sa, &splan, kVjp, nullptr))) return rc;
   if (!outputs_ok(o)) return fail(MCPX_EINVAL, "required output arrays missing");
   if (!ct) return fail(MCPX_EINVAL, "the cotangent must be non-NULL");
   if (d->batch == 0) return MCPX_OK;
@@ -1167,13 +828,12 @@ int solve_vjp_device_impl(const mcpx_desc* d, const double* theta, const double*
   if ((rc = current_device(&dev))) return rc;
   const hipStream_t st = (hipStream_t)stream;
   const int n = d->n, m = d->m;
-  if (!wg && specialized_enabled() && mcpx::has_fused_vjp(a.family, a.solver, n, m)) {
-    const int64_t CH = (int64_t)1 << 30;
+  if (!plan.wg && specialized_enabled() && mcpx::has_fused_vjp(a.family, a.solver, n, m)) {
     a.ct_ax = ct->ax;
     a.ct_ay = ct->ay;
     a.ct_as = ct->as;
-    for (int64_t b0 = 0; b0 < d->batch; b0 += CH) {
-      const int64_t nb = std::min(CH, d->batch - b0);
+    for (int64_t b0 = 0; b0 < d->batch; b0 += wg::kChunk) {
+      const int64_t nb = std::min(wg::kChunk, d->batch - b0);
       set_chunk(a, d, theta, x0, y0, s0, o, b0);
       a.vjp_dtheta = dtheta + b0 * sa.p;
       a.vjp_status = vstat ? vstat + b0 : nullptr;
@@ -1184,47 +844,36 @@ int solve_vjp_device_impl(const mcpx_desc* d, const double* theta, const double*
     }
     return MCPX_OK;
   }
-  if ((rc = launch_chunks(d, theta, x0, y0, s0, o, a, nmax, st, nullptr, wg))) return rc;
+  if ((rc = launch_chunks(d, theta, x0, y0, s0, o, a, plan, st))) return rc;
+  sa.theta = theta;
+  sa.x = o->x;
+  sa.y = o->y;
+  sa.s = o->s;
+  sa.gx = ct->bx;
+  sa.gy = ct->by;
+  sa.gs = ct->bs;
+  sa.out = dtheta;
+  sa.status = vstat;
   sa.ga_x = ct->ax;
   sa.ga_y = ct->ay;
   sa.ga_s = ct->as;
-  return launch_sens(false, d, sa, plan, theta, o->x, o->y, o->s, ct->bx, ct->by, ct->bs, nullptr, dtheta, vstat, st);
+  return launch_sens(false, d, sa, splan, st);
 }
 
-// mcpx_solve_batch / mcpx_solve_batch_module: contiguous shards, one host thread per device.
+// mcpx_solve_batch / mcpx_solve_batch_module: contiguous shards over the devices.
 int solve_host_impl(mcpx_module* mod, const mcpx_desc* d, const double* theta, const double* x0,
                     const double* y0, const double* s0, const mcpx_params* prm, int num_devices,
                     mcpx_out* o) {
   mcpx::KernelArgs a;
-  int nmax;
-  int rc = prepare(d, prm, &a, &nmax, mod);
+  SolvePlan plan;
+  int rc = prepare(d, prm, &a, &plan, mod);
   if (rc) return rc;
   if (!outputs_ok(o)) return fail(MCPX_EINVAL, "required output arrays missing");
   if (d->batch == 0) return MCPX_OK;
   if (!theta) return fail(MCPX_EINVAL, "theta is NULL");
-  const int avail = mcpx_device_count();
-  if (avail < 1) return fail(MCPX_ENODEV, "no HIP device visible");
-  if (num_devices <= 0 || num_devices > avail) num_devices = avail;
-  if ((int64_t)num_devices > d->batch) num_devices = (int)d->batch;
-  const int devs = num_devices;
-  num_devices = host_shards(devs, d->batch);
-  // contiguous shards: shard g (device g mod devs) gets ⌊B/G⌋ (+1 for g < B mod G)
-  std::vector<int64_t> start(num_devices + 1, 0);
-  for (int g = 0; g < num_devices; ++g)
-    start[g + 1] = start[g] + d->batch / num_devices + (g < d->batch % num_devices ? 1 : 0);
-  if (num_devices == 1) return solve_shard(0, d, theta, x0, y0, s0, prm, o, 0, d->batch, mod);
-  std::vector<int> rcs(num_devices, 0);
-  std::vector<std::string> errs(num_devices);
-  std::vector<std::thread> th;
-  for (int g = 0; g < num_devices; ++g)
-    th.emplace_back([&, g] {
-      rcs[g] = solve_shard(g % devs, d, theta, x0, y0, s0, prm, o, start[g], start[g + 1] - start[g], mod);
-      if (rcs[g]) errs[g] = g_err;
-    });
-  for (auto& t : th) t.join();
-  for (int g = 0; g < num_devices; ++g)
-    if (rcs[g]) return fail(rcs[g], "device %d: %s", g, errs[g].c_str());
-  return MCPX_OK;
+  return run_shards(num_devices, d->batch, [&](int dev, int64_t b0, int64_t nb) {
+    return solve_shard(dev, d, theta, x0, y0, s0, a, plan, o, b0, nb);
+  });
 }
 
 }  // namespace
@@ -1295,74 +944,102 @@ int mcpx_host_unregister(void* ptr) {
 int mcpx_vjp_batch_device(const mcpx_desc* d, const double* theta, const double* x, const double* y,
                           const double* s, const double* gx, const double* gy, const double* gs, double* dtheta,
                           int32_t* status, void* stream) {
-  return vjp_device_impl(nullptr, d, theta, x, y, s, gx, gy, gs, dtheta, status, stream);
+  mcpx::SensArgs a = sens_args(theta, x, y, s, dtheta, status);
+  a.gx = gx;
+  a.gy = gy;
+  a.gs = gs;
+  return sens_device(kVjp, nullptr, d, a, stream);
 }
 
 int mcpx_vjp_batch(const mcpx_desc* d, const double* theta, const double* x, const double* y, const double* s,
                    const double* gx, const double* gy, const double* gs, int num_devices, double* dtheta,
                    int32_t* status) {
-  return vjp_host_impl(nullptr, d, theta, x, y, s, gx, gy, gs, num_devices, dtheta, status);
+  mcpx::SensArgs a = sens_args(theta, x, y, s, dtheta, status);
+  a.gx = gx;
+  a.gy = gy;
+  a.gs = gs;
+  return sens_host(kVjp, nullptr, d, a, num_devices);
 }
 
 int mcpx_jvp_batch_device(const mcpx_desc* d, const double* theta, const double* x, const double* y,
                           const double* s, int32_t n_partials, const double* theta_dot, double* zdot,
                           int32_t* status, void* stream) {
-  return jvp_device_impl(nullptr, d, theta, x, y, s, n_partials, theta_dot, zdot, status, stream);
+  mcpx::SensArgs a = sens_args(theta, x, y, s, zdot, status);
+  a.n_partials = n_partials;
+  a.theta_dot = theta_dot;
+  return sens_device(kJvp, nullptr, d, a, stream);
 }
 
 int mcpx_jvp_batch(const mcpx_desc* d, const double* theta, const double* x, const double* y, const double* s,
                    int32_t n_partials, const double* theta_dot, int num_devices, double* zdot, int32_t* status) {
-  return jvp_host_impl(nullptr, d, theta, x, y, s, n_partials, theta_dot, num_devices, zdot, status);
+  mcpx::SensArgs a = sens_args(theta, x, y, s, zdot, status);
+  a.n_partials = n_partials;
+  a.theta_dot = theta_dot;
+  return sens_host(kJvp, nullptr, d, a, num_devices);
 }
 
 int mcpx_cond_batch(const mcpx_desc* d, const double* theta, const double* x, const double* y, const double* s,
                     int num_devices, double* rcond, int32_t* status) {
-  return cond_host_impl(nullptr, d, theta, x, y, s, num_devices, rcond, status);
+  return sens_host(kCond, nullptr, d, sens_args(theta, x, y, s, rcond, status), num_devices);
 }
 
 int mcpx_cond_batch_device(const mcpx_desc* d, const double* theta, const double* x, const double* y,
                            const double* s, double* rcond, int32_t* status, void* stream) {
-  return cond_device_impl(nullptr, d, theta, x, y, s, rcond, status, stream);
+  return sens_device(kCond, nullptr, d, sens_args(theta, x, y, s, rcond, status), stream);
 }
 
 int mcpx_cond_batch_module(mcpx_module* mod, const mcpx_desc* d, const double* theta, const double* x,
                            const double* y, const double* s, int num_devices, double* rcond, int32_t* status) {
   if (!mod) return fail(MCPX_EINVAL, "module is NULL");
-  return cond_host_impl(mod, d, theta, x, y, s, num_devices, rcond, status);
+  return sens_host(kCond, mod, d, sens_args(theta, x, y, s, rcond, status), num_devices);
 }
 
 int mcpx_cond_batch_module_device(mcpx_module* mod, const mcpx_desc* d, const double* theta, const double* x,
                                   const double* y, const double* s, double* rcond, int32_t* status, void* stream) {
   if (!mod) return fail(MCPX_EINVAL, "module is NULL");
-  return cond_device_impl(mod, d, theta, x, y, s, rcond, status, stream);
+  return sens_device(kCond, mod, d, sens_args(theta, x, y, s, rcond, status), stream);
 }
 
 int mcpx_vjp_batch_module(mcpx_module* mod, const mcpx_desc* d, const double* theta, const double* x,
                           const double* y, const double* s, const double* gx, const double* gy, const double* gs,
                           int num_devices, double* dtheta, int32_t* status) {
   if (!mod) return fail(MCPX_EINVAL, "module is NULL");
-  return vjp_host_impl(mod, d, theta, x, y, s, gx, gy, gs, num_devices, dtheta, status);
+  mcpx::SensArgs a = sens_args(theta, x, y, s, dtheta, status);
+  a.gx = gx;
+  a.gy = gy;
+  a.gs = gs;
+  return sens_host(kVjp, mod, d, a, num_devices);
 }
 
 int mcpx_vjp_batch_module_device(mcpx_module* mod, const mcpx_desc* d, const double* theta, const double* x,
                                  const double* y, const double* s, const double* gx, const double* gy,
                                  const double* gs, double* dtheta, int32_t* status, void* stream) {
   if (!mod) return fail(MCPX_EINVAL, "module is NULL");
-  return vjp_device_impl(mod, d, theta, x, y, s, gx, gy, gs, dtheta, status, stream);
+  mcpx::SensArgs a = sens_args(theta, x, y, s, dtheta, status);
+  a.gx = gx;
+  a.gy = gy;
+  a.gs = gs;
+  return sens_device(kVjp, mod, d, a, stream);
 }
 
 int mcpx_jvp_batch_module(mcpx_module* mod, const mcpx_desc* d, const double* theta, const double* x,
                           const double* y, const double* s, int32_t n_partials, const double* theta_dot,
                           int num_devices, double* zdot, int32_t* status) {
   if (!mod) return fail(MCPX_EINVAL, "module is NULL");
-  return jvp_host_impl(mod, d, theta, x, y, s, n_partials, theta_dot, num_devices, zdot, status);
+  mcpx::SensArgs a = sens_args(theta, x, y, s, zdot, status);
+  a.n_partials = n_partials;
+  a.theta_dot = theta_dot;
+  return sens_host(kJvp, mod, d, a, num_devices);
 }
 
 int mcpx_jvp_batch_module_device(mcpx_module* mod, const mcpx_desc* d, const double* theta, const double* x,
                                  const double* y, const double* s, int32_t n_partials, const double* theta_dot,
                                  double* zdot, int32_t* status, void* stream) {
   if (!mod) return fail(MCPX_EINVAL, "module is NULL");
-  return jvp_device_impl(mod, d, theta, x, y, s, n_partials, theta_dot, zdot, status, stream);
+  mcpx::SensArgs a = sens_args(theta, x, y, s, zdot, status);
+  a.n_partials = n_partials;
+  a.theta_dot = theta_dot;
+  return sens_device(kJvp, mod, d, a, stream);
 }
 
 // ---- generated nonlinear modules (MCPX_FAMILY_NONLINEAR) ----------------------
@@ -1410,9 +1087,9 @@ int mcpx_module_load(const char* path, mcpx_module** out) {
     return fail(MCPX_EINVAL, "'%s' is not an mcpx nonlinear module (no mcpx_nl_meta)", path);
   }
   HIP_TRY(hipMemcpyDtoH(mod->meta, dp, bytes));
-  if (mod->meta[0] != kNLLayout) {
+  if (mod->meta[kMetaLayout] != kNLLayout) {
     (void)hipModuleUnload(hm);
-    return fail(MCPX_EINVAL, "module layout version %d, this library expects %d", mod->meta[0], kNLLayout);
+    return fail(MCPX_EINVAL, "module layout version %d, this library expects %d", mod->meta[kMetaLayout], kNLLayout);
   }
   *out = mod.release();
   return MCPX_OK;
@@ -1420,10 +1097,10 @@ int mcpx_module_load(const char* path, mcpx_module** out) {
 
 int mcpx_module_dims(const mcpx_module* mod, int32_t* n, int32_t* m, int32_t* p, int32_t* solvers) {
   if (!mod) return fail(MCPX_EINVAL, "module is NULL");
-  if (n) *n = mod->meta[1];
-  if (m) *m = mod->meta[2];
-  if (p) *p = mod->meta[3];
-  if (solvers) *solvers = mod->meta[5];
+  if (n) *n = mod->meta[kMetaN];
+  if (m) *m = mod->meta[kMetaM];
+  if (p) *p = mod->meta[kMetaP];
+  if (solvers) *solvers = mod->meta[kMetaKernels];
   return MCPX_OK;
 }
 

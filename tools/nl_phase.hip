@@ -12,6 +12,7 @@
 #include <vector>
 #include "../mcp_amd/csrc/ipm_kernel.h"
 #include "../mcp_amd/csrc/ipm_wg.h"
+#include "../mcp_amd/csrc/wg_layout.h"
 
 int main(int argc, char** argv) {
   if (argc < 8) { fprintf(stderr, "usage\n"); return 2; }
@@ -61,14 +62,8 @@ int main(int argc, char** argv) {
     int per_cu = 0, cus = 0;
     (void)hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, K, threads, 0);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0);
-    auto align = [](int64_t v) { return (v + 31) / 32 * 32; };
-    const int ns = n;
-    w.ld = ns + 1;
-    w.off_blk = align((int64_t)ns * w.ld);
-    w.off_aux = align(w.off_blk + meta[6]);
-    w.off_rd = w.off_aux;
-    w.slot_stride = align(w.off_aux + 4 * (int64_t)m);
-    grid = (unsigned)std::min<int64_t>((int64_t)std::max(per_cu, 1) * std::max(cus, 1), B);
+    w = mcpx::wg::solve_layout(MCPX_LINSOLVE_SCHUR, n, m, meta[6]);  // meta[6]: the module's block size
+    grid = (unsigned)mcpx::wg::grid_size((int64_t)std::max(per_cu, 1) * std::max(cus, 1), B, w.slot_stride, 0);
     double* ws = nullptr;
     (void)hipMalloc(&ws, sizeof(double) * (size_t)(grid * w.slot_stride) + 256);
     w.work = ws;

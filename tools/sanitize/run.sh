@@ -19,7 +19,9 @@ gcc -std=c11 -ffp-contract=off $SAN -I"$ROOT/include" "$ROOT/oracle/ipm_oracle.c
 /opt/rocm/bin/hipcc -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fPIC -Xarch_host -fsanitize=address \
     -Xarch_host -fsanitize=undefined -Xarch_host -fno-omit-frame-pointer -g -c "$ROOT/mcp_amd/csrc/mcpx_api.cpp" \
     -o "$OUT/mcpx_api_san.o"
-/opt/rocm/lib/llvm/bin/clang++ -std=c++17 -fsanitize=address,undefined -g "$ROOT/tools/sanitize/abi_checks.cpp" \
+# (abi_checks.cpp is host-only C++: it takes wg_layout.h, and with it the HIP headers, as plain clang++)
+/opt/rocm/lib/llvm/bin/clang++ -std=c++17 -fsanitize=address,undefined -g -D__HIP_PLATFORM_AMD__ \
+    -I/opt/rocm/include "$ROOT/tools/sanitize/abi_checks.cpp" \
     "$OUT/mcpx_api_san.o" -L"$ROOT/mcp_amd" -lmcpx -L/opt/rocm/lib -lamdhip64 \
     -Wl,-rpath,"$ROOT/mcp_amd" -Wl,-rpath,/opt/rocm/lib -lpthread -o "$OUT/abi_checks"
 "$OUT/abi_checks"
