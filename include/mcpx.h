@@ -58,6 +58,10 @@ extern "C" {
  * struct, so the major version moved.  Callers check mcpx_version() / 10000 against
  * MCPX_VERSION / 10000 before the first call (mcp_amd/_lib.py does). */
 #define MCPX_VERSION 20200 /* 2.1.0: mcpx_cond_batch*; 2.2.0: MCPX_FAIL_INPUT */
+/* The shared-matrix entries (mcpx_theta_shared_dim, mcpx_theta_var_dim, mcpx_solve_batch_shared,
+ * mcpx_solve_batch_shared_device) were added under 2.2.0 without a version step: no struct and no
+ * existing function changed, so every 2.x caller keeps working; a caller that needs them looks
+ * the symbols up. */
 
 /* error codes */
 #define MCPX_OK 0
@@ -202,6 +206,13 @@ const char* mcpx_last_error(void);
 void mcpx_default_params(mcpx_params* prm);
 /* θ dimension p of a family at (n, m); < 0 on bad input. */
 int64_t mcpx_theta_dim(int32_t family, int32_t n, int32_t m);
+/* The split of θ′ for shared-matrix batches (QP and affine families; < 0 on bad input, and
+ * for MCPX_FAMILY_NONLINEAR, whose θ is the module's own).  θ′ is cut at one offset:
+ *   QP      shared [vec(M); vec(A)]                   n² + m·n          per instance [b; ϕ]  m + n
+ *   affine  shared [vec(P); vec(Q); vec(R); vec(S)]   n² + 2nm + m²     per instance [g; h]  n + m
+ * so shared ‖ var_b is instance b's θ′, and shared_dim + var_dim = mcpx_theta_dim. */
+int64_t mcpx_theta_shared_dim(int32_t family, int32_t n, int32_t m);
+int64_t mcpx_theta_var_dim(int32_t family, int32_t n, int32_t m);
 /* number of visible HIP devices (0 when none) */
 int mcpx_device_count(void);
 /* Debug: with MCPX_POISON=1 in the environment every device block the library allocates for
@@ -223,6 +234,28 @@ int64_t mcpx_debug_canary_violations(void);
 int mcpx_solve_batch(const mcpx_desc* desc, const double* theta,
                      const double* x0, const double* y0, const double* s0,
                      const mcpx_params* prm, int num_devices, mcpx_out* out);
+
+/* Shared-matrix batches: every instance has the same matrix block and its own vectors.
+ * `theta_shared` holds mcpx_theta_shared_dim doubles ONCE; `theta_var` holds instance b's
+ * mcpx_theta_var_dim doubles at theta_var + b·desc->theta_ld — in these two calls
+ * desc->theta_ld is the stride of theta_var (>= mcpx_theta_var_dim; padding is never read).
+ * Contract: every output field is bit-identical to mcpx_solve_batch[_device] on the
+ * materialised θ′ (shared ‖ var_b per instance).  Everything else is as in those calls: warm
+ * starts, params, outputs, size limits, kernel selection, MCPX_ENODEV, the pipeline knobs and
+ * num_devices.  MCPX_EINVAL: MCPX_FAMILY_NONLINEAR; NULL theta_shared or theta_var with
+ * batch > 0.  The shared block must not alias an output array.
+ * The host call uploads the shared block once per device and sends only theta_var (and warm
+ * starts) through the chunk pipeline.  QP family with MCPX_LINSOLVE_SCHUR on one wave: the
+ * kernels read the two blocks in place.  Every other combination: θ′ is materialised on the
+ * device, a slice of at most MCPX_EXPAND_MB MiB (environment, default 256) at a time, and
+ * the kernels of the full-θ call run on each slice. */
+int mcpx_solve_batch_shared(const mcpx_desc* desc, const double* theta_shared, const double* theta_var,
+                            const double* x0, const double* y0, const double* s0,
+                            const mcpx_params* prm, int num_devices, mcpx_out* out);
+/* The same on device buffers of the current device, enqueued on `stream`. */
+int mcpx_solve_batch_shared_device(const mcpx_desc* desc, const double* theta_shared, const double* theta_var,
+                                   const double* x0, const double* y0, const double* s0,
+                                   const mcpx_params* prm, const mcpx_out* out, void* stream);
 
 /* Page-lock a caller-owned host range (hipHostRegister, all devices) so that the
  * host-buffer calls read it by asynchronous DMA; optional, for long-lived θ

@@ -124,3 +124,20 @@ def theta_dim(family: int, n: int, m: int) -> int:
     if family == FAMILY_NONLINEAR:
         raise ValueError("a nonlinear MCP's θ dimension is its own (NLSystem.p, mcpx_module_dims)")
     raise ValueError(f"unknown family {family}")
+
+
+def theta_shared_dim(family: int, n: int, m: int) -> int:
+    """Doubles of the matrix block of θ′ that a shared-matrix batch passes once
+    (mcpx_theta_shared_dim): QP [vec(M); vec(A)], affine [vec(P); vec(Q); vec(R); vec(S)]."""
+    if family == FAMILY_QP:
+        return n * n + m * n
+    if family == FAMILY_AFFINE:
+        return n * n + 2 * n * m + m * m
+    if family == FAMILY_NONLINEAR:
+        raise ValueError("a nonlinear MCP's θ is its own: it has no shared-matrix split")
+    raise ValueError(f"unknown family {family}")
+
+
+def theta_var_dim(family: int, n: int, m: int) -> int:
+    """Doubles of the per-instance block (mcpx_theta_var_dim): QP [b; ϕ], affine [g; h]."""
+    return theta_dim(family, n, m) - theta_shared_dim(family, n, m)

@@ -32,7 +32,8 @@ EXPORTS = ("mcpx_version", "mcpx_last_error", "mcpx_default_params", "mcpx_theta
            "mcpx_host_register", "mcpx_host_unregister", "mcpx_vjp_batch_module", "mcpx_vjp_batch_module_device",
            "mcpx_jvp_batch_module", "mcpx_jvp_batch_module_device", "mcpx_solve_vjp_batch_device",
            "mcpx_cond_batch", "mcpx_cond_batch_device", "mcpx_cond_batch_module", "mcpx_cond_batch_module_device",
-           "mcpx_debug_canary_violations")
+           "mcpx_debug_canary_violations", "mcpx_theta_shared_dim", "mcpx_theta_var_dim",
+           "mcpx_solve_batch_shared", "mcpx_solve_batch_shared_device")
 
 
 ABI_MAJOR = 2  # include/mcpx.h MCPX_VERSION / 10000
@@ -64,6 +65,15 @@ def lib():
                                           C.c_void_p, C.POINTER(_abi.Params), C.POINTER(_abi.Out),
                                           C.c_void_p]
     P = C.c_void_p
+    for f in (L.mcpx_theta_shared_dim, L.mcpx_theta_var_dim):
+        f.restype = C.c_int64
+        f.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.mcpx_solve_batch_shared.restype = C.c_int
+    L.mcpx_solve_batch_shared.argtypes = [C.POINTER(_abi.Desc), P, P, P, P, P, C.POINTER(_abi.Params), C.c_int,
+                                          C.POINTER(_abi.Out)]
+    L.mcpx_solve_batch_shared_device.restype = C.c_int
+    L.mcpx_solve_batch_shared_device.argtypes = [C.POINTER(_abi.Desc), P, P, P, P, P, C.POINTER(_abi.Params),
+                                                 C.POINTER(_abi.Out), C.c_void_p]
     L.mcpx_vjp_batch.restype = C.c_int
     L.mcpx_vjp_batch.argtypes = [C.POINTER(_abi.Desc), P, P, P, P, P, P, P, C.c_int, P, P]
     L.mcpx_vjp_batch_device.restype = C.c_int

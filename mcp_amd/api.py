@@ -142,6 +142,15 @@ class ThetaMap:
                 const[i] = float(poly.coeff_monomial(1))
             else:
                 nonlin.append((i, e))
+        thetas = list(thetas)
+        self._nonlin = [(i, sp.lambdify(thetas, e, "numpy"), e) for i, e in nonlin]
+        self._nonlin_grad = [(i, [(thetas.index(t), sp.lambdify(thetas, sp.diff(e, t), "numpy"))
+                                  for t in e.free_symbols if t in thetas]) for i, e in nonlin]
+        self._thetas = thetas
+        self._set_terms(const, dst, src, coef)
+
+    def _set_terms(self, const, dst, src, coef):
+        """The constants and linear terms (with self.p_in, p_out and _nonlin set)."""
         self.const = const
         self.dst = np.asarray(dst, np.int64)
         self.src = np.asarray(src, np.int64)
@@ -155,16 +164,30 @@ class ThetaMap:
         self._groups = [np.nonzero(rank == r)[0] for r in range(int(rank.max()) + 1 if len(dst) else 0)]
         self._has_lin = np.zeros(self.p_out, bool)
         self._has_lin[self.dst] = True
-        thetas = list(thetas)
-        self._nonlin = [(i, sp.lambdify(thetas, e, "numpy"), e) for i, e in nonlin]
-        self._nonlin_grad = [(i, [(thetas.index(t), sp.lambdify(thetas, sp.diff(e, t), "numpy"))
-                                  for t in e.free_symbols if t in thetas]) for i, e in nonlin]
-        self._thetas = thetas
         # identity fast path: θ' is a permutation-free copy of θ
-        self.identity = (not nonlin and self.p_in == self.p_out and len(dst) == self.p_out
+        self.identity = (not self._nonlin and self.p_in == self.p_out and len(dst) == self.p_out
                          and np.array_equal(self.dst, np.arange(self.p_out))
                          and np.array_equal(self.src, np.arange(self.p_out)) and np.all(self.coef == 1.0)
                          and np.all(const == 0.0))
+
+    def split(self, D: int):
+        """(shared, var_map) when θ'[:D] does not depend on θ — no linear and no lambdified
+        term below D — else None.  shared: those D constants; var_map: the ThetaMap of the
+        other entries, var_map(θ) == self(θ)[:, D:] bit for bit (the same terms in the same
+        order).  What a shared-matrix batch passes once and per instance
+        (batch.solve_batch_shared: D = _abi.theta_shared_dim)."""
+        D = int(D)
+        if not 0 <= D <= self.p_out:
+            raise ValueError(f"split offset {D} outside θ' (dimension {self.p_out})")
+        if np.any(self.dst < D) or any(i < D for i, _, _ in self._nonlin):
+            return None
+        var = object.__new__(ThetaMap)
+        var.p_in, var.p_out = self.p_in, self.p_out - D
+        var._nonlin = [(i - D, f, e) for i, f, e in self._nonlin]
+        var._nonlin_grad = [(i - D, g) for i, g in self._nonlin_grad]
+        var._thetas = self._thetas
+        var._set_terms(self.const[D:].copy(), list(self.dst - D), list(self.src), list(self.coef))
+        return self.const[:D].copy(), var
 
     # -- evaluation ---------------------------------------------------------
     def __call__(self, theta):
@@ -470,6 +493,17 @@ class PrimalDualMCP:
         out[:n + m] = np.asarray(self._nl_host_theta()(*x, *y, *th), float).reshape(n + m, p)
         return out
 
+    def shared_split(self):
+        """(shared, var_map) of a QP / affine MCP whose matrix block of θ' is constant — the
+        batch then shares its matrices and only [b; ϕ] (affine: [g; h]) varies per instance
+        (ThetaMap.split at _abi.theta_shared_dim) — else None.  Computed once."""
+        if self.family == _abi.FAMILY_NONLINEAR:
+            return None
+        if not hasattr(self, "_shared_split"):
+            self._shared_split = self.theta_map.split(_abi.theta_shared_dim(
+                self.family, self.unconstrained_dimension, self.constrained_dimension))
+        return self._shared_split
+
     def family_parameters(self, θ):
         """θ → θ' (the per-instance data the kernel reads), numpy or torch."""
         return self.theta_map(θ)
@@ -629,10 +663,16 @@ def solve(solver_type, mcp=None, θ=None, *, x0=None, y0=None, s0=None, tol=1e-4
 
     th = np.asarray(θ, dtype=np.float64)
     single = th.ndim == 1
-    tp = mcp.theta_map(th)
-    B = tp.shape[0]
-    r = solve_batch(mcp.family, n, m, tp, x0=x0, y0=y0, s0=s0, params=prm, num_devices=num_devices,
-                    trace_len=trace_len, module=mcp.module() if mcp.nl is not None else None)
+    split = mcp.shared_split()
+    if split is not None:  # constant matrices: one shared block, [b; ϕ] / [g; h] per instance (the same bits)
+        from .batch import solve_batch_shared
+
+        r = solve_batch_shared(mcp.family, n, m, split[0], split[1](th), x0=x0, y0=y0, s0=s0, params=prm,
+                               num_devices=num_devices, trace_len=trace_len)
+    else:
+        r = solve_batch(mcp.family, n, m, mcp.theta_map(th), x0=x0, y0=y0, s0=s0, params=prm,
+                        num_devices=num_devices, trace_len=trace_len,
+                        module=mcp.module() if mcp.nl is not None else None)
     if verbose:  # the warnings of src/solver.jl:85,97 from the per-instance failure events
         fr = r["fail_reason"]
         for b in np.nonzero(fr & (_abi.FAIL_LINSOLVE | _abi.FAIL_LINESEARCH))[0][:16]:
@@ -661,10 +701,21 @@ def _solve_device(mcp, θ, prm, x0, y0, s0, trace_len):
     from .batch import solve_batch_device
 
     th = θ if θ.dim() == 2 else θ[None, :]
-    tp = mcp.theta_map(th)
     n, m = mcp.unconstrained_dimension, mcp.constrained_dimension
-    out = solve_batch_device(mcp.family, n, m, tp, x0=x0, y0=y0, s0=s0, params=prm, trace_len=trace_len,
-                             module=mcp.module() if mcp.nl is not None else None)
+    split = mcp.shared_split()
+    if split is not None:  # constant matrices: uploaded once per device, [b; ϕ] / [g; h] mapped on device
+        import torch
+        from .batch import solve_batch_shared_device
+
+        cache = mcp.__dict__.setdefault("_shared_dev", {})
+        shared = cache.get(th.device)
+        if shared is None:
+            shared = cache[th.device] = torch.from_numpy(split[0]).to(th.device)
+        out = solve_batch_shared_device(mcp.family, n, m, shared, split[1](th), x0=x0, y0=y0, s0=s0, params=prm,
+                                        trace_len=trace_len)
+    else:
+        out = solve_batch_device(mcp.family, n, m, mcp.theta_map(th), x0=x0, y0=y0, s0=s0, params=prm,
+                                 trace_len=trace_len, module=mcp.module() if mcp.nl is not None else None)
     return MCPSolution(out["status"], out["x"], out["y"], out["s"], out["kkt_error"], out["eps"],
                        out["outer_iters"], out.get("newton_iters"), out.get("active_mask"),
                        out.get("alpha_trace"), θ=th, params=prm, mcp=mcp)

@@ -78,18 +78,8 @@ def alloc_host_outputs(B: int, n: int, m: int, trace_len: int = 0) -> dict:
     return r
 
 
-def solve_batch(family: int, n: int, m: int, theta, *, x0=None, y0=None, s0=None, params=None,
-                num_devices: int = 0, trace_len: int = 0, module: Module | None = None, out: dict | None = None,
-                **kw) -> dict:
-    """Solve B instances on the GPU(s).  theta: (B, ≥p) float64 host array.  `out`: result
-    buffers from alloc_host_outputs (filled in place and returned), else fresh arrays."""
-    theta = np.ascontiguousarray(theta, dtype=np.float64)
-    if theta.ndim == 1:
-        theta = theta[None, :]
-    B, ld = theta.shape
-    prm = _params(params, **kw)
-    conv = lambda a, k: None if a is None else np.ascontiguousarray(np.broadcast_to(a, (B, k)), dtype=np.float64)
-    x0, y0, s0 = conv(x0, n), conv(y0, m), conv(s0, m)
+def _host_out(B: int, n: int, m: int, trace_len: int, out: dict | None):
+    """The result arrays of a host-buffer solve (`out` when given, else fresh) and their mcpx_out."""
     words = max(1, (m + 63) // 64)
     if out is not None:
         r = out
@@ -106,10 +96,25 @@ def solve_batch(family: int, n: int, m: int, theta, *, x0=None, y0=None, s0=None
             fail_reason=np.empty(B, np.uint8),
         )
     fr = r.get("fail_reason")
-    out = _abi.Out(_ptr(r["x"]), _ptr(r["y"]), _ptr(r["s"]), _ptr(r["kkt_error"]), _ptr(r["eps"]),
-                   _ptr(r["outer_iters"]), _ptr(r["status"]), _ptr(r["newton_iters"]),
-                   _ptr(r["active_mask"]), _ptr(r["alpha_trace"]) if trace_len > 0 else None,
-                   int(trace_len), 0, _ptr(fr) if fr is not None else None)
+    return r, _abi.Out(_ptr(r["x"]), _ptr(r["y"]), _ptr(r["s"]), _ptr(r["kkt_error"]), _ptr(r["eps"]),
+                      _ptr(r["outer_iters"]), _ptr(r["status"]), _ptr(r["newton_iters"]),
+                      _ptr(r["active_mask"]), _ptr(r["alpha_trace"]) if trace_len > 0 else None,
+                      int(trace_len), 0, _ptr(fr) if fr is not None else None)
+
+
+def solve_batch(family: int, n: int, m: int, theta, *, x0=None, y0=None, s0=None, params=None,
+                num_devices: int = 0, trace_len: int = 0, module: Module | None = None, out: dict | None = None,
+                **kw) -> dict:
+    """Solve B instances on the GPU(s).  theta: (B, ≥p) float64 host array.  `out`: result
+    buffers from alloc_host_outputs (filled in place and returned), else fresh arrays."""
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    if theta.ndim == 1:
+        theta = theta[None, :]
+    B, ld = theta.shape
+    prm = _params(params, **kw)
+    conv = lambda a, k: None if a is None else np.ascontiguousarray(np.broadcast_to(a, (B, k)), dtype=np.float64)
+    x0, y0, s0 = conv(x0, n), conv(y0, m), conv(s0, m)
+    r, out = _host_out(B, n, m, trace_len, out)
     desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(ld))
     if module is not None:  # MCPX_FAMILY_NONLINEAR: the problem's generated code object
         check(lib().mcpx_solve_batch_module(module.handle, C.byref(desc), _ptr(theta), _ptr(x0), _ptr(y0),
@@ -117,6 +122,31 @@ def solve_batch(family: int, n: int, m: int, theta, *, x0=None, y0=None, s0=None
     else:
         check(lib().mcpx_solve_batch(C.byref(desc), _ptr(theta), _ptr(x0), _ptr(y0), _ptr(s0),
                                      C.byref(prm), int(num_devices), C.byref(out)))
+    return r
+
+
+def solve_batch_shared(family: int, n: int, m: int, theta_shared, theta_var, *, x0=None, y0=None, s0=None,
+                       params=None, num_devices: int = 0, trace_len: int = 0, out: dict | None = None, **kw) -> dict:
+    """solve_batch for a batch that shares its matrices (mcpx_solve_batch_shared; QP and affine
+    families).  theta_shared: the _abi.theta_shared_dim doubles every instance has in common,
+    once; theta_var: (B, ≥ _abi.theta_var_dim) — [b; ϕ] (QP) or [g; h] (affine) per instance.
+    Every field equals solve_batch on the materialised [theta_shared ‖ theta_var] bit for bit;
+    only theta_var crosses the host link per instance."""
+    theta_shared = np.ascontiguousarray(theta_shared, dtype=np.float64).reshape(-1)
+    if theta_shared.size != _abi.theta_shared_dim(family, n, m):
+        raise ValueError(f"theta_shared has {theta_shared.size} entries, the family's shared block has "
+                         f"{_abi.theta_shared_dim(family, n, m)}")
+    theta_var = np.ascontiguousarray(theta_var, dtype=np.float64)
+    if theta_var.ndim == 1:
+        theta_var = theta_var[None, :]
+    B, ld = theta_var.shape
+    prm = _params(params, **kw)
+    conv = lambda a, k: None if a is None else np.ascontiguousarray(np.broadcast_to(a, (B, k)), dtype=np.float64)
+    x0, y0, s0 = conv(x0, n), conv(y0, m), conv(s0, m)
+    r, o = _host_out(B, n, m, trace_len, out)
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(ld))
+    check(lib().mcpx_solve_batch_shared(C.byref(desc), _ptr(theta_shared), _ptr(theta_var), _ptr(x0), _ptr(y0),
+                                        _ptr(s0), C.byref(prm), int(num_devices), C.byref(o)))
     return r
 
 
@@ -190,6 +220,38 @@ def solve_batch_device(family: int, n: int, m: int, theta, out: dict | None = No
     else:
         check(lib().mcpx_solve_batch_device(C.byref(desc), dp(theta), dp(x0), dp(y0), dp(s0), C.byref(prm),
                                             C.byref(o), C.c_void_p(st.cuda_stream)))
+    return out
+
+
+def solve_batch_shared_device(family: int, n: int, m: int, theta_shared, theta_var, out: dict | None = None, *,
+                              x0=None, y0=None, s0=None, params=None, trace_len: int = 0, stream=None, **kw) -> dict:
+    """solve_batch_device for a batch that shares its matrices (mcpx_solve_batch_shared_device):
+    theta_shared a contiguous float64 device tensor of _abi.theta_shared_dim entries, theta_var
+    a contiguous (B, ≥ _abi.theta_var_dim) one.  Enqueued on the current stream, no
+    synchronisation; the bits of solve_batch_device on the materialised θ′."""
+    import torch
+
+    ok = lambda t: t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    if not (ok(theta_var) and theta_var.dim() == 2):
+        raise ValueError("theta_var must be a contiguous (B, n + m) float64 device tensor")
+    if not (ok(theta_shared) and theta_shared.numel() == _abi.theta_shared_dim(family, n, m)):
+        raise ValueError("theta_shared must be a contiguous float64 device tensor of theta_shared_dim entries")
+    B, ld = theta_var.shape
+    if out is None:
+        out = alloc_device_outputs(B, n, m, theta_var.device, trace_len)
+    for t in (x0, y0, s0):
+        if t is not None and not ok(t):
+            raise ValueError("warm starts must be contiguous float64 device tensors")
+    dp = lambda t: None if t is None else t.data_ptr()
+    tl = 0 if out.get("alpha_trace") is None else out["alpha_trace"].shape[1]
+    o = _abi.Out(dp(out["x"]), dp(out["y"]), dp(out["s"]), dp(out["kkt_error"]), dp(out["eps"]),
+                 dp(out["outer_iters"]), dp(out["status"]), dp(out.get("newton_iters")),
+                 dp(out.get("active_mask")), dp(out.get("alpha_trace")), int(tl), 0, dp(out.get("fail_reason")))
+    prm = _params(params, **kw)
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(ld))
+    st = stream if stream is not None else torch.cuda.current_stream(theta_var.device)
+    check(lib().mcpx_solve_batch_shared_device(C.byref(desc), dp(theta_shared), dp(theta_var), dp(x0), dp(y0), dp(s0),
+                                               C.byref(prm), C.byref(o), C.c_void_p(st.cuda_stream)))
     return out
 
 

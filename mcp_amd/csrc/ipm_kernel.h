@@ -50,6 +50,10 @@ struct KernelArgs {
   const double* ct_by;
   const double* ct_bs;
   double ct_ax, ct_ay, ct_as;  // a (scalars)
+  // shared-matrix batches (mcpx_solve_batch_shared*, the SHARED kernels only): `theta` is the one
+  // [vec(M); vec(A)] block of every instance, [b; ϕ] of instance i is at theta_var + i·var_ld
+  const double* theta_var;
+  int64_t var_ld;
 };
 
 // Launchers of the register-resident solver: one 64-lane wave (= one
@@ -69,5 +73,15 @@ hipError_t launch_ipm_dense_aff(int nmax, const KernelArgs& a, int64_t batch, hi
 hipError_t launch_ipm_fused_vjp(int family, int solver, int n, int m, const KernelArgs& a, int64_t batch,
                                 hipStream_t st);
 bool has_fused_vjp(int family, int solver, int n, int m);
+// The QP family's SCHUR solve on a shared matrix block (a.theta: [vec(M); vec(A)] once,
+// a.theta_var / a.var_ld: [b; ϕ] per instance): the compile-time sizes (2, 2), (16, 8), (32, 16)
+// (ipm_inst_shared_spec.hip; hipErrorNotFound otherwise) and the runtime-(n, m) kernels
+// (ipm_inst_shared_schur.hip).
+hipError_t launch_ipm_shared_spec(int n, int m, const KernelArgs& a, int64_t batch, hipStream_t st);
+hipError_t launch_ipm_shared_schur(int nmax, const KernelArgs& a, int64_t batch, hipStream_t st);
+// θ′ expansion (theta_expand.hip): out[i·out_ld + j] = j < ds ? shared[j] : var[i·var_ld + j − ds]
+// for i < nb, j < ds + dv; out_ld even and `out` 16-byte aligned (vector stores).
+hipError_t launch_theta_expand(const double* shared, const double* var, int64_t var_ld, double* out, int64_t out_ld,
+                               int64_t ds, int64_t dv, int64_t nb, hipStream_t st);
 
 }  // namespace mcpx

@@ -1164,11 +1164,17 @@ __device__ __forceinline__ void schur_rows_from_2d(const d4 (&acc)[NT][NT], int 
 //      others exit at once.
 // FUSE > 0 (ipm_inst_fused.hip): the instance's rrule pullback runs in the epilogue
 // (fused_vjp, register width FUSE ≥ n + m) once its solve is final — mcpx_solve_vjp_batch_device.
-template <int NMAX, int FAMILY, int NC, int MC, int SOLVER, int PASS, int FUSE = 0>
+// SHARED (QP SCHUR only; ipm_inst_shared_*.hip): args.theta is ONE [vec(M); vec(A)] block read by
+// every instance, and [b; ϕ] of instance i is at args.theta_var + i·args.var_ld
+// (mcpx_solve_batch_shared*).  Only addresses change: the arithmetic, and so every output
+// bit, is that of the kernel without the flag on the materialised θ′.
+template <int NMAX, int FAMILY, int NC, int MC, int SOLVER, int PASS, int FUSE = 0, bool SHARED = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? MCPX_FAST_WAVES : 1, 8))) void ipm_solve_kernel(const KernelArgs args) {
   constexpr bool RED = SOLVER != MCPX_LINSOLVE_DENSE;  // lanes [0,n) x, [n,n+m) (y, s)
   constexpr bool SCH = SOLVER == MCPX_LINSOLVE_SCHUR;
   static_assert(SCH || PASS == 0, "two-pass launch is for the SCHUR solver only");
+  static_assert(!SHARED || (SCH && FAMILY == MCPX_FAMILY_QP && FUSE == 0),
+                "the shared-θ read exists for the QP family's SCHUR solve without the fused pullback");
   if constexpr (PASS == 2) {
     if (__builtin_amdgcn_readfirstlane(args.status[blockIdx.x]) != STATUS_DEFERRED) return;
   }
@@ -1210,7 +1216,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
   const int lane = threadIdx.x;
   const int64_t inst = blockIdx.x;
   const int n0 = NC ? NC : args.n, m0 = MC ? MC : args.m;
-  const double* const th0 = args.theta + inst * args.theta_ld;
+  const double* th0_;
+  if constexpr (SHARED) th0_ = args.theta;  // the one [vec(M); vec(A)] block
+  else th0_ = args.theta + inst * args.theta_ld;
+  const double* const th0 = th0_;
   const double tol = args.tol;
   if constexpr (AFF) {  // −Qᵀ (row i at sQ[i·(m+1)]), then −h, −g
     const int n = n0, m = m0, ldq = m + 1;
@@ -1241,7 +1250,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
     const double* tg = th0 + NC * NC + (AFF ? NC * MC : 0);  // A | the affine R
 #pragma unroll
     for (int i = lane; i < NC * MC; i += 64) sA[(i / MC) * LDA + i % MC] = tg[i];
-    if constexpr (!AFF)
+    if constexpr (SHARED) {  // b, ϕ: this instance's own
+      const double* tv = args.theta_var + inst * args.var_ld;
+      for (int i = lane; i < MC + NC; i += 64) sA[NC * LDA + i] = tv[i];
+    } else if constexpr (!AFF)
       for (int i = lane; i < MC + NC; i += 64) sA[NC * LDA + i] = tg[NC * MC + i];
   }
   if constexpr (LDSM) {
@@ -1321,7 +1333,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
       // the negated G-side coupling and the constants (QP: A itself, then b, ϕ)
       const int ldq = AFF ? m + 1 : lda;
       const double* const tq = AFF ? (const double*)sQ : ta;
-      const double* const tb = AFF ? (const double*)sQ + n * ldq : ta + n * lda;
+      const double* tb_;
+      if constexpr (SHARED && !LDSA) tb_ = args.theta_var + inst * args.var_ld;  // [b; ϕ] of this instance
+      else tb_ = AFF ? (const double*)sQ + n * ldq : ta + n * lda;
+      const double* const tb = tb_;
       const double* const tm = LDSM ? (const double*)sM : th;  // the M block
       const int ln = opaque_lane(lane);
       // ---- F!, ∇F_z! (:79-81) --------------------------------------------
@@ -1555,15 +1570,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
 }
 
 // Launch helper used by the instantiation units.
-template <int NMAX, int FAMILY, int NC, int MC, int SOLVER, int FUSE = 0>
+template <int NMAX, int FAMILY, int NC, int MC, int SOLVER, int FUSE = 0, bool SHARED = false>
 hipError_t launch_one(const KernelArgs& args, int64_t batch, hipStream_t stream) {
   if constexpr (SOLVER == MCPX_LINSOLVE_SCHUR) {  // fast pass, then the deferred instances
-    hipLaunchKernelGGL((ipm_solve_kernel<NMAX, FAMILY, NC, MC, SOLVER, 1, FUSE>), dim3((unsigned)batch), dim3(64), 0,
+    hipLaunchKernelGGL((ipm_solve_kernel<NMAX, FAMILY, NC, MC, SOLVER, 1, FUSE, SHARED>), dim3((unsigned)batch), dim3(64), 0,
                        stream, args);
-    hipLaunchKernelGGL((ipm_solve_kernel<NMAX, FAMILY, NC, MC, SOLVER, 2, FUSE>), dim3((unsigned)batch), dim3(64), 0,
+    hipLaunchKernelGGL((ipm_solve_kernel<NMAX, FAMILY, NC, MC, SOLVER, 2, FUSE, SHARED>), dim3((unsigned)batch), dim3(64), 0,
                        stream, args);
   } else {
-    hipLaunchKernelGGL((ipm_solve_kernel<NMAX, FAMILY, NC, MC, SOLVER, 0, FUSE>), dim3((unsigned)batch), dim3(64), 0,
+    hipLaunchKernelGGL((ipm_solve_kernel<NMAX, FAMILY, NC, MC, SOLVER, 0, FUSE, SHARED>), dim3((unsigned)batch), dim3(64), 0,
                        stream, args);
   }
   return hipGetLastError();

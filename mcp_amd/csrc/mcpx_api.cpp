@@ -124,8 +124,9 @@ constexpr Wording kSolveWords = {"solves", "runs", "mcpx_solve_batch_module*"};
 constexpr Wording kSensWords = {"differentiates", "is differentiated", "mcpx_vjp_batch_module / mcpx_jvp_batch_module"};
 
 // The descriptor checks shared by the solves and the sensitivities; *pd: the θ dimension
-// (of the family, or of the generated module `mod`).
-int check_desc(const mcpx_desc* d, const mcpx_module* mod, int64_t* pd, const Wording& w) {
+// (of the family, or of the generated module `mod`); `split` (mcpx_solve_batch_shared*): of the
+// family's per-instance block, the stride desc->theta_ld then counts.
+int check_desc(const mcpx_desc* d, const mcpx_module* mod, int64_t* pd, const Wording& w, bool split = false) {
   if (mod) {  // a generated nonlinear module: θ dimension and sizes from its metadata
     if (d->family != MCPX_FAMILY_NONLINEAR)
       return fail(MCPX_EINVAL, "a generated module %s family MCPX_FAMILY_NONLINEAR (got %d)", w.does, d->family);
@@ -136,7 +137,7 @@ int check_desc(const mcpx_desc* d, const mcpx_module* mod, int64_t* pd, const Wo
   } else {
     if (d->family == MCPX_FAMILY_NONLINEAR)
       return fail(MCPX_EINVAL, "family MCPX_FAMILY_NONLINEAR %s through its generated module (%s)", w.goes, w.entry);
-    *pd = mcpx_theta_dim(d->family, d->n, d->m);
+    *pd = split ? mcpx_theta_var_dim(d->family, d->n, d->m) : mcpx_theta_dim(d->family, d->n, d->m);
   }
   if (*pd < 0) return fail(MCPX_EINVAL, "bad family %d or negative dimensions (n=%d, m=%d)", d->family, d->n, d->m);
   if (d->n + d->m < 1) return fail(MCPX_EINVAL, "empty problem (n = m = 0)");
@@ -155,12 +156,14 @@ struct SolvePlan {
 };
 
 // Validates desc/params; fills the scalar part + tables of the kernel args and the plan.
-int prepare(const mcpx_desc* d, const mcpx_params* p, mcpx::KernelArgs* a, SolvePlan* plan, mcpx_module* mod) {
+// `split`: a shared-matrix call (desc->theta_ld is the stride of the per-instance block).
+int prepare(const mcpx_desc* d, const mcpx_params* p, mcpx::KernelArgs* a, SolvePlan* plan, mcpx_module* mod,
+            bool split = false) {
   *plan = SolvePlan{};
   plan->mod = mod;
   if (!d || !p) return fail(MCPX_EINVAL, "desc and params must be non-NULL");
   int64_t pd;
-  if (const int rc = check_desc(d, mod, &pd, kSolveWords)) return rc;
+  if (const int rc = check_desc(d, mod, &pd, kSolveWords, split)) return rc;
   const int ls = p->linear_solver;
   if (ls != MCPX_LINSOLVE_REDUCED && ls != MCPX_LINSOLVE_DENSE && ls != MCPX_LINSOLVE_SCHUR)
     return fail(MCPX_EINVAL, "unknown linear_solver %d", ls);
@@ -430,6 +433,83 @@ int launch_chunks(const mcpx_desc* d, const double* theta, const double* x0, con
   return MCPX_OK;
 }
 
+// The outputs of the instances from b0 on (the host layout of set_chunk's device pointers).
+mcpx_out out_at(const mcpx_out* o, int n, int m, int64_t b0) {
+  mcpx_out r = *o;
+  r.x = o->x + b0 * n;
+  r.y = o->y + b0 * m;
+  r.s = o->s + b0 * m;
+  r.kkt_error = o->kkt_error + b0;
+  r.eps = o->eps + b0;
+  r.outer_iters = o->outer_iters + b0;
+  r.status = o->status + b0;
+  r.newton_iters = o->newton_iters ? o->newton_iters + b0 : nullptr;
+  r.active_mask = o->active_mask ? o->active_mask + b0 * mask_words(m) : nullptr;
+  r.alpha_trace = o->alpha_trace ? o->alpha_trace + b0 * (int64_t)o->trace_len * 2 : nullptr;
+  r.fail_reason = o->fail_reason ? o->fail_reason + b0 : nullptr;
+  return r;
+}
+
+// Bytes of the θ′ expansion block of a shared-matrix call (below): MCPX_EXPAND_MB MiB (A/B and
+// test knob, ≥ 1), default 256 MiB — at C3's 12.7 KB per instance 21,000 instances per slice,
+// enough to fill the device many times over, and a bound that does not grow with the batch.
+int64_t expand_cap() {
+  const char* e = std::getenv("MCPX_EXPAND_MB");
+  const long long v = e ? std::atoll(e) : 256;
+  return (int64_t)(v < 1 ? 1 : v) << 20;
+}
+
+// A shared-matrix batch (mcpx_solve_batch_shared*) on device buffers: instance i's θ′ is
+// `shared` (one copy) followed by var + i·d->theta_ld.
+//   * QP family, SCHUR, one wave: the SHARED kernels read the two blocks in place;
+//   * everything else: slices of at most expand_cap() bytes of materialised θ′ (theta_expand.hip)
+//     in one block of the device cache, each solved by the kernels of the full-θ call before the
+//     next slice overwrites it (stream order).
+// Both give the bits of launch_chunks on the materialised θ′.
+int launch_shared_chunks(const mcpx_desc* d, const double* shared, const double* var, const double* x0,
+                         const double* y0, const double* s0, const mcpx_out* o, mcpx::KernelArgs a,
+                         const SolvePlan& plan, hipStream_t st) {
+  const int n = d->n, m = d->m;
+  if (a.family == MCPX_FAMILY_QP && a.solver == MCPX_LINSOLVE_SCHUR && !plan.wg) {
+    for (int64_t b0 = 0; b0 < d->batch; b0 += wg::kChunk) {
+      const int64_t nb = std::min(wg::kChunk, d->batch - b0);
+      set_chunk(a, d, var, x0, y0, s0, o, b0);
+      a.theta_var = a.theta;
+      a.var_ld = d->theta_ld;
+      a.theta = shared;
+      a.theta_ld = 0;
+      hipError_t e = specialized_enabled() ? mcpx::launch_ipm_shared_spec(n, m, a, nb, st) : hipErrorNotFound;
+      if (e == hipErrorNotFound) e = mcpx::launch_ipm_shared_schur(plan.nmax, a, nb, st);
+      HIP_TRY(e);
+    }
+    return MCPX_OK;
+  }
+  const int64_t ds = mcpx_theta_shared_dim(d->family, n, m), dv = mcpx_theta_var_dim(d->family, n, m);
+  const int64_t ld = (ds + dv + 1) & ~(int64_t)1;  // even: every row starts 16-byte aligned
+  const int64_t fit = expand_cap() / (ld * (int64_t)sizeof(double));  // instances the block holds
+  const int64_t slice = std::max<int64_t>(1, std::min<int64_t>(d->batch, fit));
+  double* blk = nullptr;
+  HIP_TRY(dev_alloc((void**)&blk, sizeof(double) * (size_t)(slice * ld), st));
+  int rc = MCPX_OK;
+  mcpx_desc dd = *d;
+  dd.theta_ld = ld;
+  a.theta_ld = ld;
+  for (int64_t b0 = 0; b0 < d->batch && rc == MCPX_OK; b0 += slice) {
+    dd.batch = std::min(slice, d->batch - b0);
+    const hipError_t e =
+        mcpx::launch_theta_expand(shared, var + b0 * d->theta_ld, d->theta_ld, blk, ld, ds, dv, dd.batch, st);
+    if (e != hipSuccess) {
+      rc = fail(MCPX_EHIP, "theta expansion launch failed: %s", hipGetErrorString(e));
+      break;
+    }
+    const mcpx_out od = out_at(o, n, m, b0);
+    rc = launch_chunks(&dd, blk, x0 ? x0 + b0 * n : nullptr, y0 ? y0 + b0 * m : nullptr, s0 ? s0 + b0 * m : nullptr,
+                       &od, a, plan, st);
+  }
+  dev_release(blk, st);
+  return rc;
+}
+
 bool outputs_ok(const mcpx_out* o) {
   return o && o->x && o->y && o->s && o->kkt_error && o->eps && o->outer_iters && o->status &&
          o->trace_len >= 0;
@@ -457,9 +537,12 @@ int64_t host_chunk() {
 // compute stream runs chunk c once its upload is done (event), and the upload of chunk
 // c + NB waits for chunk c's kernel to release its buffer (event).  Outputs land in
 // whole-shard device buffers and come back once, after the last kernel.
-int solve_shard(int dev, const mcpx_desc* d, const double* theta, const double* x0, const double* y0,
-                const double* s0, const mcpx::KernelArgs& a, const SolvePlan& plan, mcpx_out* o, int64_t b0,
-                int64_t nb) {
+// `shared` (mcpx_solve_batch_shared): the one matrix block of a shared-matrix batch, uploaded
+// once ahead of the first chunk; `theta` is then the per-instance block (stride d->theta_ld)
+// and the only part of θ′ that goes through the rotating buffers.
+int solve_shard(int dev, const mcpx_desc* d, const double* shared, const double* theta, const double* x0,
+                const double* y0, const double* s0, const mcpx::KernelArgs& a, const SolvePlan& plan, mcpx_out* o,
+                int64_t b0, int64_t nb) {
   HIP_TRY(hipSetDevice(dev));
   int rc = check_device(dev);
   if (rc) return rc;
@@ -474,7 +557,7 @@ int solve_shard(int dev, const mcpx_desc* d, const double* theta, const double* 
   const int64_t ld = d->theta_ld;
   hipStream_t cs = P->comp, us = P->up;
   AsyncBuf<double> th[kMaxHostBufs], wx[kMaxHostBufs], wy[kMaxHostBufs], ws[kMaxHostBufs];
-  AsyncBuf<double> x, y, s, kkt, eps;
+  AsyncBuf<double> sh, x, y, s, kkt, eps;
   AsyncBuf<int32_t> outer, status, newton;
   AsyncBuf<uint64_t> am;
   AsyncBuf<uint8_t> tr, fr;
@@ -494,6 +577,10 @@ int solve_shard(int dev, const mcpx_desc* d, const double* theta, const double* 
     if (y0) HIP_TRY(wy[k].alloc((size_t)ch * m, cs));
     if (s0) HIP_TRY(ws[k].alloc((size_t)ch * m, cs));
   }
+  const int64_t ds = shared ? mcpx_theta_shared_dim(d->family, n, m) : 0;
+  // the last instance of a chunk of the per-instance block: its own doubles, not the stride
+  const int64_t tail = shared ? mcpx_theta_var_dim(d->family, n, m) : ld;
+  if (shared) HIP_TRY(sh.alloc((size_t)std::max<int64_t>(ds, 1), cs));
   HIP_TRY(x.alloc((size_t)nb * n, cs)); HIP_TRY(y.alloc((size_t)nb * m, cs)); HIP_TRY(s.alloc((size_t)nb * m, cs));
   HIP_TRY(kkt.alloc(nb, cs)); HIP_TRY(eps.alloc(nb, cs)); HIP_TRY(outer.alloc(nb, cs));
   HIP_TRY(status.alloc(nb, cs));
@@ -508,11 +595,14 @@ int solve_shard(int dev, const mcpx_desc* d, const double* theta, const double* 
   // the allocations (compute stream) before the first upload into them
   HIP_TRY(hipEventRecord(P->consumed[0], cs));
   HIP_TRY(hipStreamWaitEvent(us, P->consumed[0], 0));
+  // the shared block: once, on the upload stream ahead of chunk 0 (whose event covers it)
+  if (shared && ds > 0) HIP_TRY(hipMemcpyAsync(sh.p, shared, sizeof(double) * (size_t)ds, hipMemcpyHostToDevice, us));
   for (int64_t c0 = 0, ci = 0; c0 < nb; c0 += ch, ++ci) {
     const int k = (int)(ci % nbuf);
     const int64_t cn = std::min(ch, nb - c0), g0 = b0 + c0;
     if (ci >= nbuf) HIP_TRY(hipStreamWaitEvent(us, P->consumed[k], 0));  // chunk ci - nbuf released buffer k
-    HIP_TRY(hipMemcpyAsync(th[k].p, theta + g0 * ld, sizeof(double) * (size_t)cn * ld, hipMemcpyHostToDevice, us));
+    HIP_TRY(hipMemcpyAsync(th[k].p, theta + g0 * ld, sizeof(double) * (size_t)((cn - 1) * ld + tail),
+                           hipMemcpyHostToDevice, us));
     if (x0) HIP_TRY(hipMemcpyAsync(wx[k].p, x0 + g0 * n, sizeof(double) * cn * n, hipMemcpyHostToDevice, us));
     if (y0) HIP_TRY(hipMemcpyAsync(wy[k].p, y0 + g0 * m, sizeof(double) * cn * m, hipMemcpyHostToDevice, us));
     if (s0) HIP_TRY(hipMemcpyAsync(ws[k].p, s0 + g0 * m, sizeof(double) * cn * m, hipMemcpyHostToDevice, us));
@@ -527,7 +617,9 @@ int solve_shard(int dev, const mcpx_desc* d, const double* theta, const double* 
     od.fail_reason = fr.p ? fr.p + c0 : nullptr;
     mcpx_desc dd = *d;
     dd.batch = cn;
-    if ((rc = launch_chunks(&dd, th[k].p, wx[k].p, wy[k].p, ws[k].p, &od, a, plan, cs))) return rc;
+    rc = shared ? launch_shared_chunks(&dd, sh.p, th[k].p, wx[k].p, wy[k].p, ws[k].p, &od, a, plan, cs)
+                : launch_chunks(&dd, th[k].p, wx[k].p, wy[k].p, ws[k].p, &od, a, plan, cs);
+    if (rc) return rc;
     HIP_TRY(hipEventRecord(P->consumed[k], cs));
   }
   HIP_TRY(hipStreamSynchronize(us));
@@ -872,8 +964,20 @@ int solve_host_impl(mcpx_module* mod, const mcpx_desc* d, const double* theta, c
   if (d->batch == 0) return MCPX_OK;
   if (!theta) return fail(MCPX_EINVAL, "theta is NULL");
   return run_shards(num_devices, d->batch, [&](int dev, int64_t b0, int64_t nb) {
-    return solve_shard(dev, d, theta, x0, y0, s0, a, plan, o, b0, nb);
+    return solve_shard(dev, d, nullptr, theta, x0, y0, s0, a, plan, o, b0, nb);
   });
+}
+
+// mcpx_solve_batch_shared[_device]: the checks of the full-θ calls with the per-instance
+// dimension in θ′'s place (a generated module's θ is the user's own: MCPX_EINVAL).
+int prepare_shared(const mcpx_desc* d, const double* shared, const double* var, const mcpx_params* prm,
+                   const mcpx_out* o, mcpx::KernelArgs* a, SolvePlan* plan, bool* empty) {
+  const int rc = prepare(d, prm, a, plan, nullptr, true);
+  if (rc) return rc;
+  if (!outputs_ok(o)) return fail(MCPX_EINVAL, "required output arrays missing");
+  *empty = d->batch == 0;
+  if (!*empty && (!shared || !var)) return fail(MCPX_EINVAL, "theta_shared or theta_var is NULL");
+  return MCPX_OK;
 }
 
 }  // namespace
@@ -905,6 +1009,19 @@ int64_t mcpx_theta_dim(int32_t family, int32_t n, int32_t m) {
   return -1;
 }
 
+int64_t mcpx_theta_shared_dim(int32_t family, int32_t n, int32_t m) {
+  if (n < 0 || m < 0) return -1;
+  if (family == MCPX_FAMILY_QP) return (int64_t)n * n + (int64_t)m * n;
+  if (family == MCPX_FAMILY_AFFINE) return (int64_t)n * n + 2 * (int64_t)n * m + (int64_t)m * m;
+  return -1;
+}
+
+int64_t mcpx_theta_var_dim(int32_t family, int32_t n, int32_t m) {
+  if (n < 0 || m < 0) return -1;
+  if (family == MCPX_FAMILY_QP || family == MCPX_FAMILY_AFFINE) return (int64_t)n + m;
+  return -1;
+}
+
 int mcpx_device_count(void) {
   int c = 0;
   if (hipGetDeviceCount(&c) != hipSuccess) return 0;
@@ -927,6 +1044,32 @@ int mcpx_solve_vjp_batch_device(const mcpx_desc* d, const double* theta, const d
 int mcpx_solve_batch(const mcpx_desc* d, const double* theta, const double* x0, const double* y0,
                      const double* s0, const mcpx_params* prm, int num_devices, mcpx_out* o) {
   return solve_host_impl(nullptr, d, theta, x0, y0, s0, prm, num_devices, o);
+}
+
+int mcpx_solve_batch_shared_device(const mcpx_desc* d, const double* theta_shared, const double* theta_var,
+                                   const double* x0, const double* y0, const double* s0, const mcpx_params* prm,
+                                   const mcpx_out* o, void* stream) {
+  mcpx::KernelArgs a;
+  SolvePlan plan;
+  bool empty = false;
+  int rc = prepare_shared(d, theta_shared, theta_var, prm, o, &a, &plan, &empty);
+  if (rc || empty) return rc;
+  int dev = 0;
+  if ((rc = current_device(&dev))) return rc;
+  return launch_shared_chunks(d, theta_shared, theta_var, x0, y0, s0, o, a, plan, (hipStream_t)stream);
+}
+
+int mcpx_solve_batch_shared(const mcpx_desc* d, const double* theta_shared, const double* theta_var,
+                            const double* x0, const double* y0, const double* s0, const mcpx_params* prm,
+                            int num_devices, mcpx_out* o) {
+  mcpx::KernelArgs a;
+  SolvePlan plan;
+  bool empty = false;
+  const int rc = prepare_shared(d, theta_shared, theta_var, prm, o, &a, &plan, &empty);
+  if (rc || empty) return rc;
+  return run_shards(num_devices, d->batch, [&](int dev, int64_t b0, int64_t nb) {
+    return solve_shard(dev, d, theta_shared, theta_var, x0, y0, s0, a, plan, o, b0, nb);
+  });
 }
 
 int mcpx_host_register(void* ptr, size_t bytes) {
