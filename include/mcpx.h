@@ -61,7 +61,8 @@ extern "C" {
 /* The shared-matrix entries (mcpx_theta_shared_dim, mcpx_theta_var_dim, mcpx_solve_batch_shared,
  * mcpx_solve_batch_shared_device) were added under 2.2.0 without a version step: no struct and no
  * existing function changed, so every 2.x caller keeps working; a caller that needs them looks
- * the symbols up. */
+ * the symbols up.  The same holds for their sensitivities (mcpx_vjp_batch_shared[_device],
+ * mcpx_jvp_batch_shared[_device], mcpx_solve_vjp_batch_shared_device). */
 
 /* error codes */
 #define MCPX_OK 0
@@ -363,6 +364,57 @@ int mcpx_jvp_batch(const mcpx_desc* desc, const double* theta, const double* x, 
 int mcpx_jvp_batch_device(const mcpx_desc* desc, const double* theta, const double* x,
                           const double* y, const double* s, int32_t n_partials,
                           const double* theta_dot, double* zdot, int32_t* status, void* stream);
+
+/* Sensitivities of a shared-matrix batch (mcpx_solve_batch_shared*; QP and affine families)
+ * with respect to the per-instance block only.  `theta_shared` is the one matrix block; the
+ * calls take no theta_var: for these families ∇F_z holds M, A (affine: P, Q, R, S) and the
+ * iterate, none of b, ϕ (g, h), so nothing per instance is read from θ′.  The gradient of the
+ * per-instance block is λ itself (QP: ∂b = λ_y, ∂ϕ = λ_x; affine: ∂g = −λ_x, ∂h = −λ_y), and the
+ * rank-1 matrix blocks of the full record are neither formed nor stored.
+ *   dvar    [B × var_dim], dense stride var_dim = mcpx_theta_var_dim, in the layout of the tail
+ *           of the family's θ′: QP [∂b; ∂ϕ], affine [∂g; ∂h];
+ *   var_dot [B × n_partials × var_dim], the tangents of the per-instance block.
+ * desc->theta_ld is checked as in the shared solve (>= var_dim); only the fused call reads it,
+ * as the stride of theta_var.
+ * Contracts:
+ *   VJP    dvar[b] and status[b] equal dtheta[b][shared_dim:] and status[b] of
+ *          mcpx_vjp_batch[_device] on the materialised θ′, entry for entry, the NaN row of a
+ *          singular instance included.
+ *   JVP    zdot and status equal those of mcpx_jvp_batch[_device] with θ̇ = [0 … 0 ‖ var_dot],
+ *          for every instance whose x, y, s are finite.  The full call multiplies the zero
+ *          matrix tangent by the iterate (fma(0, z, acc)), which turns a non-finite entry of
+ *          x or y into NaN right-hand sides; the split call does not run those chains, so
+ *          there its right-hand sides are −(∇F_θ θ̇) of the per-instance block alone and a
+ *          non-finite iterate reaches the result only through the rows of ∇F_z that hold it.
+ *          That case is outside the contract.
+ *   fused  every mcpx_out field equals mcpx_solve_batch_shared_device; dvar and vjp_status
+ *          equal mcpx_vjp_batch_shared_device at that iterate with g = a ⊙ z + b (the rule of
+ *          mcpx_solve_vjp_batch_device).  QP family, SCHUR, at (2,2), (16,8), (32,16): one
+ *          launch with the pullback in the solve kernel's epilogue; every other configuration:
+ *          the shared solve, then the split pullback on out->x / y / s.
+ * The host calls upload the shared block once per device and no per-instance θ, and bring back
+ * var_dim doubles per instance; num_devices and MCPX_HOST_SHARDS are those of mcpx_vjp_batch.
+ * Errors, the empty batch, the size limit (MCPX_MAX_WG_KKT_DIM) and MCPX_ENODEV are as in the
+ * full-θ sensitivity calls; MCPX_FAMILY_NONLINEAR: MCPX_EINVAL.  (No mcpx_cond_batch on a split
+ * θ, and no reduced Σ_b ∂shared: a caller who needs ∂M or ∂A has a θ-dependent matrix block and
+ * no split.)  Added under 2.2.0 without a version step, as the shared solve entries. */
+int mcpx_vjp_batch_shared(const mcpx_desc* desc, const double* theta_shared, const double* x, const double* y,
+                          const double* s, const double* gx, const double* gy, const double* gs,
+                          int num_devices, double* dvar, int32_t* status);
+int mcpx_vjp_batch_shared_device(const mcpx_desc* desc, const double* theta_shared, const double* x,
+                                 const double* y, const double* s, const double* gx, const double* gy,
+                                 const double* gs, double* dvar, int32_t* status, void* stream);
+int mcpx_jvp_batch_shared(const mcpx_desc* desc, const double* theta_shared, const double* x, const double* y,
+                          const double* s, int32_t n_partials, const double* var_dot, int num_devices,
+                          double* zdot, int32_t* status);
+int mcpx_jvp_batch_shared_device(const mcpx_desc* desc, const double* theta_shared, const double* x,
+                                 const double* y, const double* s, int32_t n_partials,
+                                 const double* var_dot, double* zdot, int32_t* status, void* stream);
+int mcpx_solve_vjp_batch_shared_device(const mcpx_desc* desc, const double* theta_shared,
+                                       const double* theta_var, const double* x0, const double* y0,
+                                       const double* s0, const mcpx_params* prm, const mcpx_out* out,
+                                       const mcpx_cotangent* ct, double* dvar, int32_t* vjp_status,
+                                       void* stream);
 
 /* ---------------------------------------------------------------------------
  * Nonlinear G/H — MCPX_FAMILY_NONLINEAR (BASELINE C4: games, src/game.jl).

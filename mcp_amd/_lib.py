@@ -33,7 +33,9 @@ EXPORTS = ("mcpx_version", "mcpx_last_error", "mcpx_default_params", "mcpx_theta
            "mcpx_jvp_batch_module", "mcpx_jvp_batch_module_device", "mcpx_solve_vjp_batch_device",
            "mcpx_cond_batch", "mcpx_cond_batch_device", "mcpx_cond_batch_module", "mcpx_cond_batch_module_device",
            "mcpx_debug_canary_violations", "mcpx_theta_shared_dim", "mcpx_theta_var_dim",
-           "mcpx_solve_batch_shared", "mcpx_solve_batch_shared_device")
+           "mcpx_solve_batch_shared", "mcpx_solve_batch_shared_device", "mcpx_vjp_batch_shared",
+           "mcpx_vjp_batch_shared_device", "mcpx_jvp_batch_shared", "mcpx_jvp_batch_shared_device",
+           "mcpx_solve_vjp_batch_shared_device")
 
 
 ABI_MAJOR = 2  # include/mcpx.h MCPX_VERSION / 10000
@@ -85,6 +87,20 @@ def lib():
     L.mcpx_solve_vjp_batch_device.restype = C.c_int
     L.mcpx_solve_vjp_batch_device.argtypes = [C.POINTER(_abi.Desc), P, P, P, P, C.POINTER(_abi.Params),
                                               C.POINTER(_abi.Out), C.POINTER(_abi.Cotangent), P, P, C.c_void_p]
+    # sensitivities of a shared-matrix batch: the full-θ signatures with theta_shared in θ's place
+    # (the fused call: theta_shared, theta_var)
+    L.mcpx_vjp_batch_shared.restype = C.c_int
+    L.mcpx_vjp_batch_shared.argtypes = L.mcpx_vjp_batch.argtypes
+    L.mcpx_vjp_batch_shared_device.restype = C.c_int
+    L.mcpx_vjp_batch_shared_device.argtypes = L.mcpx_vjp_batch_device.argtypes
+    L.mcpx_jvp_batch_shared.restype = C.c_int
+    L.mcpx_jvp_batch_shared.argtypes = L.mcpx_jvp_batch.argtypes
+    L.mcpx_jvp_batch_shared_device.restype = C.c_int
+    L.mcpx_jvp_batch_shared_device.argtypes = L.mcpx_jvp_batch_device.argtypes
+    L.mcpx_solve_vjp_batch_shared_device.restype = C.c_int
+    L.mcpx_solve_vjp_batch_shared_device.argtypes = [C.POINTER(_abi.Desc), P, P, P, P, P, C.POINTER(_abi.Params),
+                                                     C.POINTER(_abi.Out), C.POINTER(_abi.Cotangent), P, P,
+                                                     C.c_void_p]
     I32P = C.POINTER(C.c_int32)
     L.mcpx_module_load.restype = C.c_int
     L.mcpx_module_load.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]

@@ -697,6 +697,18 @@ def solve(solver_type, mcp=None, θ=None, *, x0=None, y0=None, s0=None, tol=1e-4
                        θ=th, params=prm, mcp=mcp)
 
 
+def _shared_device(mcp, device):
+    """The device copy of mcp.shared_split()'s matrix block on `device`, uploaded once per MCP
+    and device (the shared-matrix solve and its sensitivities, autodiff.py, read the same one)."""
+    import torch
+
+    cache = mcp.__dict__.setdefault("_shared_dev", {})
+    shared = cache.get(device)
+    if shared is None:
+        shared = cache[device] = torch.from_numpy(mcp.shared_split()[0]).to(device)
+    return shared
+
+
 def _solve_device(mcp, θ, prm, x0, y0, s0, trace_len):
     from .batch import solve_batch_device
 
@@ -704,15 +716,10 @@ def _solve_device(mcp, θ, prm, x0, y0, s0, trace_len):
     n, m = mcp.unconstrained_dimension, mcp.constrained_dimension
     split = mcp.shared_split()
     if split is not None:  # constant matrices: uploaded once per device, [b; ϕ] / [g; h] mapped on device
-        import torch
         from .batch import solve_batch_shared_device
 
-        cache = mcp.__dict__.setdefault("_shared_dev", {})
-        shared = cache.get(th.device)
-        if shared is None:
-            shared = cache[th.device] = torch.from_numpy(split[0]).to(th.device)
-        out = solve_batch_shared_device(mcp.family, n, m, shared, split[1](th), x0=x0, y0=y0, s0=s0, params=prm,
-                                        trace_len=trace_len)
+        out = solve_batch_shared_device(mcp.family, n, m, _shared_device(mcp, th.device), split[1](th), x0=x0, y0=y0,
+                                        s0=s0, params=prm, trace_len=trace_len)
     else:
         out = solve_batch_device(mcp.family, n, m, mcp.theta_map(th), x0=x0, y0=y0, s0=s0, params=prm,
                                  trace_len=trace_len, module=mcp.module() if mcp.nl is not None else None)

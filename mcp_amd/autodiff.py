@@ -58,6 +58,13 @@ def _module(mcp):
     return mcp.module() if getattr(mcp, "nl", None) is not None else None
 
 
+def _split(mcp):
+    """(shared, var_map) of an MCP whose matrix block of θ' is constant (PrimalDualMCP.shared_split),
+    else None: the full-θ' sensitivity calls."""
+    f = getattr(mcp, "shared_split", None)
+    return f() if f is not None else None
+
+
 def _is_torch(a) -> bool:
     return type(a).__module__.startswith("torch")
 
@@ -75,18 +82,28 @@ def solve_pullback(solution, dx=None, dy=None, ds=None, *, num_devices: int = 0,
     returned by `solve(InteriorPoint(), mcp, θ)`.  None cotangents are zero.
     Shapes follow the solution: single instance → (p,), batch → (B, p); torch
     solutions stay on device (enqueued on the current stream)."""
-    from .batch import vjp_batch, vjp_batch_device
+    from .batch import vjp_batch, vjp_batch_device, vjp_batch_shared, vjp_batch_shared_device
 
     mcp = solution.mcp
     _require_sensitivities(mcp)
     n, m = mcp.unconstrained_dimension, mcp.constrained_dimension
     θ = solution.θ
+    # constant matrices (the solve took the shared-matrix path): the split pullback returns the
+    # gradient of the per-instance block alone, and var_map has the full map's terms in their order
+    split = _split(mcp)
     if _is_torch(θ):
         import torch
 
         th = θ if θ.dim() == 2 else θ[None, :]
-        tp = mcp.theta_map(th).contiguous()
         f = lambda t: None if t is None else t.to(torch.float64).reshape(th.shape[0], -1).contiguous()
+        if split is not None:
+            from .api import _shared_device
+
+            dv, st = vjp_batch_shared_device(mcp.family, n, m, _shared_device(mcp, th.device), f(solution.x),
+                                             f(solution.y), f(solution.s), f(dx), f(dy), f(ds))
+            dθ = split[1].vjp(th, dv)
+            return (dθ, st) if return_status else dθ
+        tp = mcp.theta_map(th).contiguous()
         dtp, st = vjp_batch_device(mcp.family, n, m, tp, f(solution.x), f(solution.y), f(solution.s),
                                    f(dx), f(dy), f(ds), module=_module(mcp))
         dθ = mcp.theta_map.vjp(th, dtp)
@@ -95,11 +112,16 @@ def solve_pullback(solution, dx=None, dy=None, ds=None, *, num_devices: int = 0,
     single = th.ndim == 1
     th2 = np.atleast_2d(th)
     B = th2.shape[0]
-    tp = mcp.theta_map(th2)
     f = lambda a, k: None if a is None else np.asarray(a, np.float64).reshape(B, k)
-    dtp, st = vjp_batch(mcp.family, n, m, tp, f(solution.x, n), f(solution.y, m), f(solution.s, m),
-                        f(dx, n), f(dy, m), f(ds, m), num_devices=num_devices, module=_module(mcp))
-    dθ = mcp.theta_map.vjp(th2, dtp)
+    if split is not None:
+        dv, st = vjp_batch_shared(mcp.family, n, m, split[0], f(solution.x, n), f(solution.y, m), f(solution.s, m),
+                                  f(dx, n), f(dy, m), f(ds, m), num_devices=num_devices)
+        dθ = split[1].vjp(th2, dv)
+    else:
+        tp = mcp.theta_map(th2)
+        dtp, st = vjp_batch(mcp.family, n, m, tp, f(solution.x, n), f(solution.y, m), f(solution.s, m),
+                            f(dx, n), f(dy, m), f(ds, m), num_devices=num_devices, module=_module(mcp))
+        dθ = mcp.theta_map.vjp(th2, dtp)
     if single:
         dθ, st = dθ[0], st[0]
     return (dθ, st) if return_status else dθ
@@ -184,7 +206,7 @@ def solve_dual(solver_type, mcp, θ, θ_partials, *, num_devices: int = 0, **kwa
     θ: (p,) or (B, p) values; θ_partials: (p, K) or (B, p, K) — the partials of
     each θ entry, as ForwardDiff.partials.(θ) stacked."""
     from .api import solve
-    from .batch import jvp_batch
+    from .batch import jvp_batch, jvp_batch_shared
 
     _require_sensitivities(mcp)
     n, m = mcp.unconstrained_dimension, mcp.constrained_dimension
@@ -194,10 +216,16 @@ def solve_dual(solver_type, mcp, θ, θ_partials, *, num_devices: int = 0, **kwa
     B, p_in = th2.shape
     tpar = np.asarray(θ_partials, np.float64).reshape(B, p_in, -1)
     sol = solve(solver_type, mcp, th2, num_devices=num_devices, **kwargs)  # forward pass (:94)
-    tp = mcp.theta_map(th2)
-    tdot = mcp.theta_map.jvp(th2, np.ascontiguousarray(np.swapaxes(tpar, 1, 2)))  # (B, K, p')
-    zd, st = jvp_batch(mcp.family, n, m, tp, sol.x, sol.y, sol.s, tdot, num_devices=num_devices,
-                       module=_module(mcp))  # (B, K, N)
+    split = _split(mcp)
+    if split is not None:  # constant matrices: tangents of the per-instance block only
+        vdot = split[1].jvp(th2, np.ascontiguousarray(np.swapaxes(tpar, 1, 2)))  # (B, K, n + m)
+        zd, st = jvp_batch_shared(mcp.family, n, m, split[0], sol.x, sol.y, sol.s, vdot,
+                                  num_devices=num_devices)  # (B, K, N)
+    else:
+        tp = mcp.theta_map(th2)
+        tdot = mcp.theta_map.jvp(th2, np.ascontiguousarray(np.swapaxes(tpar, 1, 2)))  # (B, K, p')
+        zd, st = jvp_batch(mcp.family, n, m, tp, sol.x, sol.y, sol.s, tdot, num_devices=num_devices,
+                           module=_module(mcp))  # (B, K, N)
     zp = np.swapaxes(zd, 1, 2)  # (B, N, K): z_p = ∂z∂θ · θ_p (:98)
     xp, yp, sp_ = zp[:, :n], zp[:, n:n + m], zp[:, n + m:]
     pick = (lambda a: a[0]) if single else (lambda a: a)

@@ -439,3 +439,154 @@ def jvp_batch_device(family: int, n: int, m: int, theta, x, y, s, theta_dot, zdo
              _dev_f64(td.contiguous(), "theta_dot"), _dev_f64(zdot, "zdot"), status.data_ptr(),
              C.c_void_p(st.cuda_stream)))
     return zdot, status
+
+
+# ---------------------------------------------------------------------------
+# sensitivities of a shared-matrix batch (include/mcpx.h mcpx_vjp_batch_shared* /
+# mcpx_jvp_batch_shared* / mcpx_solve_vjp_batch_shared_device): one matrix block for the
+# batch, gradients and tangents of the per-instance block [b; ϕ] (QP) / [g; h] (affine) only
+
+
+def _host_shared(family: int, n: int, m: int, theta_shared) -> np.ndarray:
+    theta_shared = np.ascontiguousarray(theta_shared, dtype=np.float64).reshape(-1)
+    if theta_shared.size != _abi.theta_shared_dim(family, n, m):
+        raise ValueError(f"theta_shared has {theta_shared.size} entries, the family's shared block has "
+                         f"{_abi.theta_shared_dim(family, n, m)}")
+    return theta_shared
+
+
+def _dev_shared(family: int, n: int, m: int, theta_shared) -> int:
+    import torch
+
+    if not (theta_shared.is_cuda and theta_shared.dtype == torch.float64 and theta_shared.is_contiguous()
+            and theta_shared.numel() == _abi.theta_shared_dim(family, n, m)):
+        raise ValueError("theta_shared must be a contiguous float64 device tensor of theta_shared_dim entries")
+    return theta_shared.data_ptr()
+
+
+def _batch_of(x, y, n: int, m: int) -> int:
+    """Instances of a split sensitivity call: the rows of x (of y when n = 0)."""
+    a = x if n > 0 else y
+    return int(a.shape[0]) if a.ndim == 2 else 1
+
+
+def vjp_batch_shared(family: int, n: int, m: int, theta_shared, x, y, s, gx=None, gy=None, gs=None,
+                     num_devices: int = 0) -> tuple:
+    """vjp_batch for a shared-matrix batch (mcpx_vjp_batch_shared): theta_shared as in
+    solve_batch_shared, no per-instance θ (∇F_z does not contain it).  Returns (dvar (B, n + m) —
+    [∂b; ∂ϕ] (QP) or [∂g; ∂h] (affine), the bits of vjp_batch(θ′)[0][:, shared_dim:] — and
+    status (B,))."""
+    theta_shared = _host_shared(family, n, m, theta_shared)
+    B = _batch_of(np.atleast_2d(np.asarray(x)), np.atleast_2d(np.asarray(y)), n, m)
+    dv = _abi.theta_var_dim(family, n, m)
+    x, y, s = _host_f64(x, (B, n)), _host_f64(y, (B, m)), _host_f64(s, (B, m))
+    gx, gy, gs = _host_f64(gx, (B, n)), _host_f64(gy, (B, m)), _host_f64(gs, (B, m))
+    dvar = np.empty((B, dv))
+    st = np.empty(B, np.int32)
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(dv))
+    check(lib().mcpx_vjp_batch_shared(C.byref(desc), _ptr(theta_shared), _ptr(x), _ptr(y), _ptr(s), _ptr(gx),
+                                      _ptr(gy), _ptr(gs), int(num_devices), _ptr(dvar), _ptr(st)))
+    return dvar, st
+
+
+def jvp_batch_shared(family: int, n: int, m: int, theta_shared, x, y, s, var_dot, num_devices: int = 0) -> tuple:
+    """jvp_batch for a shared-matrix batch (mcpx_jvp_batch_shared): var_dot (B, K, n + m), the
+    tangents of the per-instance block (the matrix block's are zero) → (zdot (B, K, n+2m),
+    status (B,)), the bits of jvp_batch on θ̇ = [0 ‖ var_dot] for finite iterates."""
+    theta_shared = _host_shared(family, n, m, theta_shared)
+    B = _batch_of(np.atleast_2d(np.asarray(x)), np.atleast_2d(np.asarray(y)), n, m)
+    dv = _abi.theta_var_dim(family, n, m)
+    vd = np.ascontiguousarray(var_dot, dtype=np.float64).reshape(B, -1, dv)
+    K = vd.shape[1]
+    x, y, s = _host_f64(x, (B, n)), _host_f64(y, (B, m)), _host_f64(s, (B, m))
+    zd = np.empty((B, K, n + 2 * m))
+    st = np.empty(B, np.int32)
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(dv))
+    check(lib().mcpx_jvp_batch_shared(C.byref(desc), _ptr(theta_shared), _ptr(x), _ptr(y), _ptr(s), int(K), _ptr(vd),
+                                      int(num_devices), _ptr(zd), _ptr(st)))
+    return zd, st
+
+
+def vjp_batch_shared_device(family: int, n: int, m: int, theta_shared, x, y, s, gx=None, gy=None, gs=None,
+                            dvar=None, status=None, stream=None):
+    """Device-tensor pullback of a shared-matrix batch, enqueued on the current stream (no sync):
+    (dvar (B, n + m), status (B,) int32) tensors."""
+    import torch
+
+    sh = _dev_shared(family, n, m, theta_shared)
+    B = _batch_of(x, y, n, m)
+    dv = _abi.theta_var_dim(family, n, m)
+    dev = theta_shared.device
+    if dvar is None:
+        dvar = torch.empty(B, dv, dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+    ptrs = [_dev_f64(t, k) for t, k in ((x, "x"), (y, "y"), (s, "s"), (gx, "gx"), (gy, "gy"), (gs, "gs"))]
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(dv))
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    check(lib().mcpx_vjp_batch_shared_device(C.byref(desc), sh, *ptrs, _dev_f64(dvar, "dvar"), status.data_ptr(),
+                                             C.c_void_p(st.cuda_stream)))
+    return dvar, status
+
+
+def jvp_batch_shared_device(family: int, n: int, m: int, theta_shared, x, y, s, var_dot, zdot=None, status=None,
+                            stream=None):
+    """Device-tensor tangents of a shared-matrix batch: var_dot (B, K, n + m) →
+    (zdot (B, K, n+2m), status (B,))."""
+    import torch
+
+    sh = _dev_shared(family, n, m, theta_shared)
+    B = _batch_of(x, y, n, m)
+    dv = _abi.theta_var_dim(family, n, m)
+    vd = var_dot.reshape(B, -1, dv)
+    K = vd.shape[1]
+    dev = theta_shared.device
+    if zdot is None:
+        zdot = torch.empty(B, K, n + 2 * m, dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(dv))
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    check(lib().mcpx_jvp_batch_shared_device(C.byref(desc), sh, _dev_f64(x, "x"), _dev_f64(y, "y"), _dev_f64(s, "s"),
+                                             int(K), _dev_f64(vd.contiguous(), "var_dot"), _dev_f64(zdot, "zdot"),
+                                             status.data_ptr(), C.c_void_p(st.cuda_stream)))
+    return zdot, status
+
+
+def solve_vjp_batch_shared_device(family: int, n: int, m: int, theta_shared, theta_var, out: dict | None = None, *,
+                                  ct=(0.0, 0.0, 0.0), bx=None, by=None, bs=None, dvar=None, status=None, x0=None,
+                                  y0=None, s0=None, params=None, stream=None, **kw):
+    """solve_vjp_batch_device for a shared-matrix batch (mcpx_solve_vjp_batch_shared_device): the
+    solve of solve_batch_shared_device into `out`, then the gradient of the per-instance block
+    for the cotangent ct[k]·z + b (as there).  Returns (out, dvar (B, n + m), status (B,))."""
+    import torch
+
+    ok = lambda t: t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    if not (ok(theta_var) and theta_var.dim() == 2):
+        raise ValueError("theta_var must be a contiguous (B, n + m) float64 device tensor")
+    sh = _dev_shared(family, n, m, theta_shared)
+    B, ld = theta_var.shape
+    dev = theta_var.device
+    if out is None:
+        out = alloc_device_outputs(B, n, m, dev)
+    if dvar is None:
+        dvar = torch.empty(B, _abi.theta_var_dim(family, n, m), dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+    for t in (x0, y0, s0):
+        if t is not None and not ok(t):
+            raise ValueError("warm starts must be contiguous float64 device tensors")
+    dp = lambda t: None if t is None else t.data_ptr()
+    tl = 0 if out.get("alpha_trace") is None else out["alpha_trace"].shape[1]
+    o = _abi.Out(dp(out["x"]), dp(out["y"]), dp(out["s"]), dp(out["kkt_error"]), dp(out["eps"]),
+                 dp(out["outer_iters"]), dp(out["status"]), dp(out.get("newton_iters")),
+                 dp(out.get("active_mask")), dp(out.get("alpha_trace")), int(tl), 0, dp(out.get("fail_reason")))
+    cot = _abi.Cotangent(float(ct[0]), float(ct[1]), float(ct[2]), _dev_f64(bx, "bx"), _dev_f64(by, "by"),
+                         _dev_f64(bs, "bs"))
+    prm = _params(params, **kw)
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(ld))
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    check(lib().mcpx_solve_vjp_batch_shared_device(C.byref(desc), sh, dp(theta_var), dp(x0), dp(y0), dp(s0),
+                                                   C.byref(prm), C.byref(o), C.byref(cot), _dev_f64(dvar, "dvar"),
+                                                   dp(status), C.c_void_p(st.cuda_stream)))
+    return out, dvar, status

@@ -79,6 +79,9 @@ bool has_fused_vjp(int family, int solver, int n, int m);
 // (ipm_inst_shared_schur.hip).
 hipError_t launch_ipm_shared_spec(int n, int m, const KernelArgs& a, int64_t batch, hipStream_t st);
 hipError_t launch_ipm_shared_schur(int nmax, const KernelArgs& a, int64_t batch, hipStream_t st);
+// That solve with the pullback fused into its epilogue (ipm_inst_shared_fused.hip), for the sizes of
+// has_fused_vjp: a.vjp_dtheta is [B × (n+m)], the gradient [∂b; ∂ϕ] of the per-instance block.
+hipError_t launch_ipm_shared_fused_vjp(int n, int m, const KernelArgs& a, int64_t batch, hipStream_t st);
 // θ′ expansion (theta_expand.hip): out[i·out_ld + j] = j < ds ? shared[j] : var[i·var_ld + j − ds]
 // for i < nb, j < ds + dv; out_ld even and `out` 16-byte aligned (vector stores).
 hipError_t launch_theta_expand(const double* shared, const double* var, int64_t var_ld, double* out, int64_t out_ld,

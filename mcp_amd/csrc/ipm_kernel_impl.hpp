@@ -1115,7 +1115,7 @@ __device__ __forceinline__ bool gj2d_spd_la(std::integer_sequence<int, K...>, do
 
 // The rrule pullback fused into the solve kernel's epilogue (defined in
 // sens_kernel_impl.hpp; only the FUSE instantiations of ipm_inst_fused.hip use it).
-template <int NV, int FAMILY, int NT, bool LU>
+template <int NV, int FAMILY, int NT, bool LU, bool SPLIT = false>
 __device__ __forceinline__ bool fused_vjp(const KernelArgs& A, int64_t inst, int ln, int n, int m, double z, double s,
                                           const double* th, const double* ta, int lda, bool msym,
                                           double* const (&lds)[5]);
@@ -1166,15 +1166,17 @@ __device__ __forceinline__ void schur_rows_from_2d(const d4 (&acc)[NT][NT], int 
 // (fused_vjp, register width FUSE ≥ n + m) once its solve is final — mcpx_solve_vjp_batch_device.
 // SHARED (QP SCHUR only; ipm_inst_shared_*.hip): args.theta is ONE [vec(M); vec(A)] block read by
 // every instance, and [b; ϕ] of instance i is at args.theta_var + i·args.var_ld
-// (mcpx_solve_batch_shared*).  Only addresses change: the arithmetic, and so every output
+// (mcpx_solve_batch_shared*); with FUSE (ipm_inst_shared_fused.hip) the pullback writes
+// [∂b; ∂ϕ] only, n + m doubles per instance at args.vjp_dtheta.  Only addresses change: the arithmetic, and so every output
 // bit, is that of the kernel without the flag on the materialised θ′.
 template <int NMAX, int FAMILY, int NC, int MC, int SOLVER, int PASS, int FUSE = 0, bool SHARED = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? MCPX_FAST_WAVES : 1, 8))) void ipm_solve_kernel(const KernelArgs args) {
   constexpr bool RED = SOLVER != MCPX_LINSOLVE_DENSE;  // lanes [0,n) x, [n,n+m) (y, s)
   constexpr bool SCH = SOLVER == MCPX_LINSOLVE_SCHUR;
   static_assert(SCH || PASS == 0, "two-pass launch is for the SCHUR solver only");
-  static_assert(!SHARED || (SCH && FAMILY == MCPX_FAMILY_QP && FUSE == 0),
-                "the shared-θ read exists for the QP family's SCHUR solve without the fused pullback");
+  static_assert(!SHARED || (SCH && FAMILY == MCPX_FAMILY_QP && (FUSE == 0 || (NC > 0 && MC > 0))),
+                "the shared-θ read exists for the QP family's SCHUR solve; with the fused pullback, for its "
+                "compile-time sizes");
   if constexpr (PASS == 2) {
     if (__builtin_amdgcn_readfirstlane(args.status[blockIdx.x]) != STATUS_DEFERRED) return;
   }
@@ -1515,7 +1517,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
     // The pullback's Schur path reuses the solve's A block (LDS copy) and its M-symmetry test
     // (opaque sizes: with constant ones the pullback's loops unroll into spills)
     double* const lds[5] = {zs, sD, sT, sB, sF};
-    const bool done = fused_vjp<FUSE, FAMILY, (NMAX + 15) / 16, PASS != 1>(
+    const bool done = fused_vjp<FUSE, FAMILY, (NMAX + 15) / 16, PASS != 1, SHARED>(
         args, inst, lane, opaque(n0), opaque(m0), z, s, th0, LDSA ? (const double*)sA : th0 + n0 * n0,
         LDSA ? LDA : m0, spd_try, lds);
     if (!done) {  // PASS 1 only (the LU pass always completes)

@@ -81,5 +81,8 @@ hipError_t launch_ipm_wg(int family, int solver, int nv, int ns, const wg::WgArg
 // n + 2m ≤ nv ∈ wg::kDimBuckets.
 const void* sens_wg_kernel(int family, bool jvp, int nv);
 hipError_t launch_sens_wg(int family, bool jvp, int nv, const wg::WgSensArgs& a, int grid, hipStream_t st);
+// The same on a shared-matrix batch (sens_inst_wg_shared.hip; sens_wg_impl.hpp SPLIT).
+const void* sens_wg_shared_kernel(int family, bool jvp, int nv);
+hipError_t launch_sens_wg_shared(int family, bool jvp, int nv, const wg::WgSensArgs& a, int grid, hipStream_t st);
 
 }  // namespace mcpx

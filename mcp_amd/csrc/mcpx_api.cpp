@@ -690,23 +690,30 @@ enum SensKind { kVjp, kJvp, kCond };
 // How a sensitivity call runs: one wave per instance (QP / affine, n + 2m ≤ 64: the
 // register kernels of sens_kernel_impl.hpp, `nmax` wide) or one workgroup per instance
 // (larger QP / affine systems in the dimension bucket `nv`, and every generated module).
+// `split`: a shared-matrix batch (mcpx_vjp_batch_shared*, mcpx_jvp_batch_shared*) — the SPLIT
+// kernels, which read one matrix block and write / read the per-instance block's n + m doubles.
 struct SensPlan {
   int nmax = 0;
   bool wg = false;
   int nv = 0;
   mcpx_module* mod = nullptr;
+  bool split = false;
 };
 
 // Validates a sensitivity call; fills the scalar part of the args (the caller's pointers,
-// n_partials and cotangent factors stay) and the plan.
-int prepare_sens(const mcpx_desc* d, mcpx::SensArgs* a, SensPlan* plan, SensKind kind, mcpx_module* mod) {
+// n_partials and cotangent factors stay) and the plan.  `split`: a shared-matrix call — desc->theta_ld
+// is checked as in the shared solve, a->p is the per-instance dimension n + m (the stride of the
+// outputs and tangents), and the kernels read a->theta for every instance.
+int prepare_sens(const mcpx_desc* d, mcpx::SensArgs* a, SensPlan* plan, SensKind kind, mcpx_module* mod,
+                 bool split = false) {
   if (!d) return fail(MCPX_EINVAL, "desc must be non-NULL");
   int64_t pd;
-  if (const int rc = check_desc(d, mod, &pd, kSensWords)) return rc;
+  if (const int rc = check_desc(d, mod, &pd, kSensWords, split)) return rc;
   const bool jvp = kind != kVjp;
   const int N = d->n + 2 * d->m;
   *plan = SensPlan{};
   plan->mod = mod;
+  plan->split = split;
   if (mod) {
     if (!mod->has(jvp ? MCPX_MODULE_JVP : MCPX_MODULE_VJP))
       return fail(MCPX_EUNSUPPORTED, "the generated module has no %s kernel (n=%d m=%d: not even a 4-column LU panel of "
@@ -722,7 +729,7 @@ int prepare_sens(const mcpx_desc* d, mcpx::SensArgs* a, SensPlan* plan, SensKind
   } else {
     return fail(MCPX_EUNSUPPORTED, "sensitivities need n + 2m <= %d (got n=%d m=%d)", MCPX_MAX_WG_KKT_DIM, d->n, d->m);
   }
-  a->theta_ld = d->theta_ld;
+  a->theta_ld = split ? 0 : d->theta_ld;
   a->p = pd;
   a->n = d->n;
   a->m = d->m;
@@ -773,15 +780,17 @@ int launch_sens_wg_impl(bool jvp, const mcpx_desc* d, const mcpx::SensArgs& a, c
     const int rc = module_function(plan.mod, name, name, &k.f, &dev);
     if (rc) return rc;
   } else {
-    k.sym = mcpx::sens_wg_kernel(a.family, jvp, plan.nv);
+    k.sym = plan.split ? mcpx::sens_wg_shared_kernel(a.family, jvp, plan.nv)
+                       : mcpx::sens_wg_kernel(a.family, jvp, plan.nv);
     if (!k.sym) return fail(MCPX_EUNSUPPORTED, "no workgroup sensitivity kernel for family %d, dim %d", a.family, plan.nv);
   }
   wg::WgSensArgs w = wg::sens_layout(jvp, a.mode, a.n, a.m, a.p, a.n_partials,
                                      plan.mod ? plan.mod->meta[kMetaBlock] : wg::kNoModule);
   return launch_persistent(k, -1, d->batch, w, wg::kSensWorkCap, st, "workgroup sensitivity", [&](int64_t b0, int grid) {
     w.s = sens_chunk(a, jvp, b0);
-    return plan.mod ? launch_module(k.f, grid, k.threads, &w, st)
-                    : mcpx::launch_sens_wg(a.family, jvp, plan.nv, w, grid, st);
+    if (plan.mod) return launch_module(k.f, grid, k.threads, &w, st);
+    return plan.split ? mcpx::launch_sens_wg_shared(a.family, jvp, plan.nv, w, grid, st)
+                      : mcpx::launch_sens_wg(a.family, jvp, plan.nv, w, grid, st);
   });
 }
 
@@ -793,12 +802,18 @@ int launch_sens(bool jvp, const mcpx_desc* d, const mcpx::SensArgs& a, const Sen
     const int64_t nb = std::min(wg::kChunk, d->batch - b0);
     const mcpx::SensArgs c = sens_chunk(a, jvp, b0);
     // the VJP factors the slack-eliminated (n+m)-dim system, the JVP the full n+2m
-    HIP_TRY(jvp ? mcpx::launch_jvp(plan.nmax, c, nb, st) : mcpx::launch_vjp(pick_nmax(a.n + a.m), c, nb, st));
+    if (plan.split)
+      HIP_TRY(jvp ? mcpx::launch_jvp_shared(plan.nmax, c, nb, st)
+                  : mcpx::launch_vjp_shared(pick_nmax(a.n + a.m), c, nb, st));
+    else
+      HIP_TRY(jvp ? mcpx::launch_jvp(plan.nmax, c, nb, st) : mcpx::launch_vjp(pick_nmax(a.n + a.m), c, nb, st));
   }
   return MCPX_OK;
 }
 
 // One device's share [b0, b0+nb) of a host-buffer sensitivity call (`a`: host pointers).
+// A shared-matrix call (plan.split) uploads its one matrix block, no per-instance θ, and brings
+// back a.p = n + m doubles per instance.
 int sens_shard(bool jvp, int dev, const mcpx_desc* d, const mcpx::SensArgs& a, const SensPlan& plan, int64_t b0,
                int64_t nb) {
   HIP_TRY(hipSetDevice(dev));
@@ -812,7 +827,13 @@ int sens_shard(bool jvp, int dev, const mcpx_desc* d, const mcpx::SensArgs& a, c
     hipError_t e = b.alloc((size_t)nb * per);
     return e != hipSuccess ? e : hipMemcpy(b.p, h + b0 * per, sizeof(double) * nb * per, hipMemcpyHostToDevice);
   };
-  HIP_TRY(up(th, a.theta, (size_t)d->theta_ld));
+  if (plan.split) {
+    const int64_t ds = mcpx_theta_shared_dim(d->family, n, m);
+    HIP_TRY(th.alloc((size_t)std::max<int64_t>(ds, 1)));
+    if (ds > 0) HIP_TRY(hipMemcpy(th.p, a.theta, sizeof(double) * (size_t)ds, hipMemcpyHostToDevice));
+  } else {
+    HIP_TRY(up(th, a.theta, (size_t)d->theta_ld));
+  }
   HIP_TRY(up(dx, a.x, n)); HIP_TRY(up(dy, a.y, m)); HIP_TRY(up(ds, a.s, m));
   HIP_TRY(up(dgx, a.gx, n)); HIP_TRY(up(dgy, a.gy, m)); HIP_TRY(up(dgs, a.gs, m));
   HIP_TRY(up(dtd, a.theta_dot, (size_t)a.n_partials * a.p));
@@ -845,11 +866,12 @@ int sens_shard(bool jvp, int dev, const mcpx_desc* d, const mcpx::SensArgs& a, c
 }
 
 // The device-buffer sensitivity entries (`a`: the caller's pointers, n_partials): enqueued
-// on `stream` of the current device.
-int sens_device(SensKind kind, mcpx_module* mod, const mcpx_desc* d, mcpx::SensArgs a, void* stream) {
+// on `stream` of the current device.  `split`: a.theta is the matrix block of a shared-matrix batch.
+int sens_device(SensKind kind, mcpx_module* mod, const mcpx_desc* d, mcpx::SensArgs a, void* stream,
+                bool split = false) {
   SensPlan plan;
   int rc;
-  if ((rc = prepare_sens(d, &a, &plan, kind, mod))) return rc;
+  if ((rc = prepare_sens(d, &a, &plan, kind, mod, split))) return rc;
   if ((rc = sens_inputs_ok(d, a)) || d->batch == 0) return rc;
   int dev = 0;
   if ((rc = current_device(&dev))) return rc;
@@ -861,10 +883,11 @@ int sens_device(SensKind kind, mcpx_module* mod, const mcpx_desc* d, mcpx::SensA
 }
 
 // The host-buffer sensitivity entries: contiguous shards over the devices.
-int sens_host(SensKind kind, mcpx_module* mod, const mcpx_desc* d, mcpx::SensArgs a, int num_devices) {
+int sens_host(SensKind kind, mcpx_module* mod, const mcpx_desc* d, mcpx::SensArgs a, int num_devices,
+              bool split = false) {
   SensPlan plan;
   int rc;
-  if ((rc = prepare_sens(d, &a, &plan, kind, mod))) return rc;
+  if ((rc = prepare_sens(d, &a, &plan, kind, mod, split))) return rc;
   if ((rc = sens_inputs_ok(d, a)) || d->batch == 0) return rc;
   return run_shards(num_devices, d->batch, [&](int dev, int64_t b0, int64_t nb) {
     return sens_shard(kind != kVjp, dev, d, a, plan, b0, nb);
@@ -945,6 +968,64 @@ int solve_vjp_device_impl(const mcpx_desc* d, const double* theta, const double*
   sa.gy = ct->by;
   sa.gs = ct->bs;
   sa.out = dtheta;
+  sa.status = vstat;
+  sa.ga_x = ct->ax;
+  sa.ga_y = ct->ay;
+  sa.ga_s = ct->as;
+  return launch_sens(false, d, sa, splan, st);
+}
+
+// mcpx_solve_vjp_batch_shared_device: the SHARED solve kernels with the pullback in their epilogue
+// (ipm_inst_shared_fused.hip) where they exist, else the shared solve (in place or through the
+// expansion block, launch_shared_chunks) then the split VJP launches on its outputs — the
+// pullback needs the matrix block only, never the expansion.
+int solve_vjp_shared_device_impl(const mcpx_desc* d, const double* shared, const double* var, const double* x0,
+                                 const double* y0, const double* s0, const mcpx_params* prm, const mcpx_out* o,
+                                 const mcpx_cotangent* ct, double* dvar, int32_t* vstat, void* stream) {
+  mcpx::KernelArgs a;
+  SolvePlan plan;
+  int rc = prepare(d, prm, &a, &plan, nullptr, true);
+  if (rc) return rc;
+  mcpx::SensArgs sa{};
+  SensPlan splan;
+  if ((rc = prepare_sens(d, &sa, &splan, kVjp, nullptr, true))) return rc;
+  if (!outputs_ok(o)) return fail(MCPX_EINVAL, "required output arrays missing");
+  if (!ct) return fail(MCPX_EINVAL, "the cotangent must be non-NULL");
+  if (d->batch == 0) return MCPX_OK;
+  if (!shared || !var || !dvar) return fail(MCPX_EINVAL, "theta_shared, theta_var and dvar must be non-NULL");
+  int dev = 0;
+  if ((rc = current_device(&dev))) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  const int n = d->n, m = d->m;
+  if (!plan.wg && specialized_enabled() && mcpx::has_fused_vjp(a.family, a.solver, n, m)) {
+    a.ct_ax = ct->ax;
+    a.ct_ay = ct->ay;
+    a.ct_as = ct->as;
+    for (int64_t b0 = 0; b0 < d->batch; b0 += wg::kChunk) {
+      const int64_t nb = std::min(wg::kChunk, d->batch - b0);
+      set_chunk(a, d, var, x0, y0, s0, o, b0);
+      a.theta_var = a.theta;
+      a.var_ld = d->theta_ld;
+      a.theta = shared;
+      a.theta_ld = 0;
+      a.vjp_dtheta = dvar + b0 * sa.p;
+      a.vjp_status = vstat ? vstat + b0 : nullptr;
+      a.ct_bx = ct->bx ? ct->bx + b0 * n : nullptr;
+      a.ct_by = ct->by ? ct->by + b0 * m : nullptr;
+      a.ct_bs = ct->bs ? ct->bs + b0 * m : nullptr;
+      HIP_TRY(mcpx::launch_ipm_shared_fused_vjp(n, m, a, nb, st));
+    }
+    return MCPX_OK;
+  }
+  if ((rc = launch_shared_chunks(d, shared, var, x0, y0, s0, o, a, plan, st))) return rc;
+  sa.theta = shared;
+  sa.x = o->x;
+  sa.y = o->y;
+  sa.s = o->s;
+  sa.gx = ct->bx;
+  sa.gy = ct->by;
+  sa.gs = ct->bs;
+  sa.out = dvar;
   sa.status = vstat;
   sa.ga_x = ct->ax;
   sa.ga_y = ct->ay;
@@ -1070,6 +1151,52 @@ int mcpx_solve_batch_shared(const mcpx_desc* d, const double* theta_shared, cons
   return run_shards(num_devices, d->batch, [&](int dev, int64_t b0, int64_t nb) {
     return solve_shard(dev, d, theta_shared, theta_var, x0, y0, s0, a, plan, o, b0, nb);
   });
+}
+
+int mcpx_solve_vjp_batch_shared_device(const mcpx_desc* d, const double* theta_shared, const double* theta_var,
+                                       const double* x0, const double* y0, const double* s0,
+                                       const mcpx_params* prm, const mcpx_out* out, const mcpx_cotangent* ct,
+                                       double* dvar, int32_t* vjp_status, void* stream) {
+  return solve_vjp_shared_device_impl(d, theta_shared, theta_var, x0, y0, s0, prm, out, ct, dvar, vjp_status,
+                                      stream);
+}
+
+int mcpx_vjp_batch_shared_device(const mcpx_desc* d, const double* theta_shared, const double* x, const double* y,
+                                 const double* s, const double* gx, const double* gy, const double* gs,
+                                 double* dvar, int32_t* status, void* stream) {
+  mcpx::SensArgs a = sens_args(theta_shared, x, y, s, dvar, status);
+  a.gx = gx;
+  a.gy = gy;
+  a.gs = gs;
+  return sens_device(kVjp, nullptr, d, a, stream, true);
+}
+
+int mcpx_vjp_batch_shared(const mcpx_desc* d, const double* theta_shared, const double* x, const double* y,
+                          const double* s, const double* gx, const double* gy, const double* gs, int num_devices,
+                          double* dvar, int32_t* status) {
+  mcpx::SensArgs a = sens_args(theta_shared, x, y, s, dvar, status);
+  a.gx = gx;
+  a.gy = gy;
+  a.gs = gs;
+  return sens_host(kVjp, nullptr, d, a, num_devices, true);
+}
+
+int mcpx_jvp_batch_shared_device(const mcpx_desc* d, const double* theta_shared, const double* x, const double* y,
+                                 const double* s, int32_t n_partials, const double* var_dot, double* zdot,
+                                 int32_t* status, void* stream) {
+  mcpx::SensArgs a = sens_args(theta_shared, x, y, s, zdot, status);
+  a.n_partials = n_partials;
+  a.theta_dot = var_dot;
+  return sens_device(kJvp, nullptr, d, a, stream, true);
+}
+
+int mcpx_jvp_batch_shared(const mcpx_desc* d, const double* theta_shared, const double* x, const double* y,
+                          const double* s, int32_t n_partials, const double* var_dot, int num_devices, double* zdot,
+                          int32_t* status) {
+  mcpx::SensArgs a = sens_args(theta_shared, x, y, s, zdot, status);
+  a.n_partials = n_partials;
+  a.theta_dot = var_dot;
+  return sens_host(kJvp, nullptr, d, a, num_devices, true);
 }
 
 int mcpx_host_register(void* ptr, size_t bytes) {

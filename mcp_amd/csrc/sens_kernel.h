@@ -41,9 +41,26 @@ __device__ __forceinline__ double affine_ct(double a, double z, const double* b)
   return b ? a * z + *b : a * z;
 }
 
+// (∇F_θ θ̇)_i of a shared-matrix batch (mcpx_jvp_batch_shared*): the tangent of the matrix
+// block is zero, so of dtheta_row() only its last step is left, on the +0.0 that the fma
+// chains over a zero tangent and a finite iterate end in.  d: this partial's [ḃ; ϕ̇]
+// (QP) or [ġ; ḣ] (affine), n + m doubles.
+template <int FAMILY>
+__device__ __forceinline__ double dvar_row(const double* __restrict__ d, int i, int n, int m) {
+  const double acc = 0.0;
+  if (i < n) return FAMILY == MCPX_FAMILY_QP ? acc - d[m + i] : acc + d[i];
+  if (i < n + m) return FAMILY == MCPX_FAMILY_QP ? acc - d[i - n] : acc + d[n + (i - n)];
+  return 0.0;
+}
+
 // One 64-lane wave per instance; nmax ∈ {8,16,24,32,48,64} ≥ n + 2m.
 // hipErrorInvalidValue when no kernel matches.
 hipError_t launch_vjp(int nmax, const SensArgs& a, int64_t batch, hipStream_t st);
 hipError_t launch_jvp(int nmax, const SensArgs& a, int64_t batch, hipStream_t st);
+// The same on a shared-matrix batch (mcpx_vjp_batch_shared*, mcpx_jvp_batch_shared*): a.theta is
+// the ONE matrix block of every instance (a.theta_ld is not read), a.out the [B × (n+m)]
+// gradient of the per-instance block / a.theta_dot its [B × K × (n+m)] tangents.
+hipError_t launch_vjp_shared(int nmax, const SensArgs& a, int64_t batch, hipStream_t st);
+hipError_t launch_jvp_shared(int nmax, const SensArgs& a, int64_t batch, hipStream_t st);
 
 }  // namespace mcpx

@@ -368,7 +368,9 @@ __device__ __forceinline__ bool vjp_qp_schur(const double* __restrict__ th, cons
 // there, `lam` its gxl).
 // LU = false (the fused fast pass): no LU fallback — returns false, writing nothing,
 // when the Schur path does not apply.
-template <int NMAX, int FAMILY, int NT = 0, bool LU = true>
+// SPLIT (a shared-matrix batch): `o` is the instance's n + m doubles of the per-instance
+// block's gradient, [∂b; ∂ϕ] / [∂g; ∂h] — λ itself; the rank-1 matrix blocks are not formed.
+template <int NMAX, int FAMILY, int NT = 0, bool LU = true, bool SPLIT = false>
 __device__ __forceinline__ bool vjp_instance(const double* __restrict__ th, const double* zs, double* lam,
                                              const double* gsv, double g, int ln, int n, int m, double* __restrict__ o,
                                              int32_t* st, const double* ta = nullptr, int lda = 0, bool msym = false,
@@ -400,6 +402,16 @@ __device__ __forceinline__ bool vjp_instance(const double* __restrict__ th, cons
   const double* y = zs + n;
   const double* lx = lam;      // λ of the G rows
   const double* ly = lam + n;  // λ of the H − s rows
+  if constexpr (SPLIT) {
+    if (FAMILY == 0) {
+      write_block(o, m, 1, ln, [&](int k, int) { return ly[k]; });        // ∂b_k
+      write_block(o + m, n, 1, ln, [&](int i, int) { return lx[i]; });    // ∂ϕ_i
+    } else {
+      write_block(o, n, 1, ln, [&](int i, int) { return -lx[i]; });       // ∂g_i
+      write_block(o + n, m, 1, ln, [&](int k, int) { return -ly[k]; });   // ∂h_k
+    }
+    return true;
+  }
   if (FAMILY == 0) {
     write_block(o, n, n, ln, [&](int i, int j) { return -(lx[i] * x[j]); });               // ∂M_ij
     write_block(o + nn, m, n, ln, [&](int k, int j) { return fma(lx[j], y[k], -(ly[k] * x[j])); });  // ∂A_kj
@@ -416,7 +428,8 @@ __device__ __forceinline__ bool vjp_instance(const double* __restrict__ th, cons
   return true;
 }
 
-template <int NMAX, int FAMILY>
+// SPLIT: A.theta is the one matrix block of a shared-matrix batch, A.out is [B × (n+m)].
+template <int NMAX, int FAMILY, bool SPLIT = false>
 __global__ __launch_bounds__(64) void vjp_kernel(const SensArgs A) {
   constexpr bool QP = FAMILY == MCPX_FAMILY_QP;
   constexpr int NT = QP ? (NMAX + 15) / 16 : 0;  // Schur path: n < NMAX
@@ -427,7 +440,10 @@ __global__ __launch_bounds__(64) void vjp_kernel(const SensArgs A) {
   const int ln = threadIdx.x;
   const int64_t inst = blockIdx.x;
   const int n = A.n, m = A.m;
-  const double* th = A.theta + inst * A.theta_ld;
+  const double* th_;
+  if constexpr (SPLIT) th_ = A.theta;
+  else th_ = A.theta + inst * A.theta_ld;
+  const double* th = th_;
   load_z(A, inst, ln, zs);
   __syncthreads();
   // ∂l/∂z_ln of the x / y rows (NULL block with a = 0: ZeroTangent)
@@ -441,8 +457,9 @@ __global__ __launch_bounds__(64) void vjp_kernel(const SensArgs A) {
     gsv = gsl;
   }
   const bool msym = QP && m_symmetric(th, ln, n);
-  vjp_instance<NMAX, FAMILY, NT>(th, zs, lam, gsv, g, ln, n, m, A.out + inst * A.p, A.status ? A.status + inst : nullptr,
-                                 th + (int64_t)n * n, m, msym, scr, scr + 64);
+  vjp_instance<NMAX, FAMILY, NT, true, SPLIT>(th, zs, lam, gsv, g, ln, n, m, A.out + inst * (SPLIT ? n + m : A.p),
+                                              A.status ? A.status + inst : nullptr, th + (int64_t)n * n, m, msym, scr,
+                                              scr + 64);
 }
 
 // The pullback fused into the solve kernel's epilogue (ipm_solve_kernel<…, FUSE = NV>):
@@ -454,7 +471,8 @@ __global__ __launch_bounds__(64) void vjp_kernel(const SensArgs A) {
 // solve's outputs, so a deferred instance leaves x/y/s untouched and a warm start read from
 // the output buffers (x0 = out.x, the receding-horizon pattern) is still intact for pass 2.
 // lds: five 64-double LDS arrays of the solve kernel, dead once its Newton loop is done.
-template <int NV, int FAMILY, int NT, bool LU>
+// SPLIT (the SHARED solve kernels): th is the shared block, A.vjp_dtheta is [B × (n+m)].
+template <int NV, int FAMILY, int NT, bool LU, bool SPLIT>
 __device__ __forceinline__ bool fused_vjp(const KernelArgs& A, int64_t inst, int ln, int n, int m, double z, double s,
                                           const double* th, const double* ta, int lda, bool msym,
                                           double* const (&lds)[5]) {
@@ -475,20 +493,25 @@ __device__ __forceinline__ bool fused_vjp(const KernelArgs& A, int64_t inst, int
     gsv = gsl;
   }
   const int64_t p = (int64_t)n * n + (int64_t)m * n + m + n;  // QP θ dimension (mcpx_theta_dim)
-  const bool done = vjp_instance<NV, FAMILY, NT, LU>(th, zs, lam, gsv, g, ln, n, m, A.vjp_dtheta + inst * p,
-                                                     A.vjp_status ? A.vjp_status + inst : nullptr, ta, lda, msym,
-                                                     lds[3], lds[4]);
+  const bool done = vjp_instance<NV, FAMILY, NT, LU, SPLIT>(
+      th, zs, lam, gsv, g, ln, n, m, A.vjp_dtheta + inst * (SPLIT ? (int64_t)(n + m) : p),
+      A.vjp_status ? A.vjp_status + inst : nullptr, ta, lda, msym, lds[3], lds[4]);
   return done;
 }
 
-template <int NMAX, int FAMILY>
+// SPLIT: A.theta is the one matrix block of a shared-matrix batch, A.theta_dot is
+// [B × K × (n+m)] (the per-instance block's tangents; the matrix block's are zero).
+template <int NMAX, int FAMILY, bool SPLIT = false>
 __global__ __launch_bounds__(64) void jvp_kernel(const SensArgs A) {
   constexpr int R = MCPX_JVP_RHS;
   __shared__ double zs[64];
   const int ln = threadIdx.x;
   const int64_t inst = blockIdx.x;
   const int n = A.n, m = A.m, N = n + 2 * m, K = A.n_partials;
-  const double* th = A.theta + inst * A.theta_ld;
+  const double* th_;
+  if constexpr (SPLIT) th_ = A.theta;
+  else th_ = A.theta + inst * A.theta_ld;
+  const double* th = th_;
   load_z(A, inst, ln, zs);
   __syncthreads();
   const RowPattern P = row_pattern<FAMILY, false>(zs, ln, n, m);
@@ -500,8 +523,12 @@ __global__ __launch_bounds__(64) void jvp_kernel(const SensArgs A) {
     for (int c = 0; c < R; ++c) {
       r[c] = 0.0;
       if (c0 + c < K) {
-        const double* d = A.theta_dot + (inst * K + c0 + c) * A.p;
-        r[c] = -dtheta_row<FAMILY>(d, P, zs, ln, n, m);
+        if constexpr (SPLIT) {
+          r[c] = -dvar_row<FAMILY>(A.theta_dot + (inst * K + c0 + c) * (n + m), ln, n, m);
+        } else {
+          const double* d = A.theta_dot + (inst * K + c0 + c) * A.p;
+          r[c] = -dtheta_row<FAMILY>(d, P, zs, ln, n, m);
+        }
       }
     }
     const bool ok = lu_solve_rows_multi<NMAX, R>(a, r, N, ln, dz);

@@ -259,9 +259,13 @@ __device__ __forceinline__ double cond_one(double* __restrict__ A, int ld, int N
 
 // NB: the panel width of the blocked LU (wg::LuShared); generated modules whose 16-column panel
 // does not fit the LDS pass 8 or 4 (csrc/ipm_nl_kernel.hpp, MCPX_NL_SENS_NB_*).
-template <int FAMILY, bool JVP, int NVMAX, int NSMAX, class GEN, int NB = kNB>
+// SPLIT (QP / affine, a shared-matrix batch: mcpx_vjp_batch_shared*, mcpx_jvp_batch_shared*):
+// a.theta is the ONE matrix block of every instance and a.p = n + m, the stride of the outputs
+// [∂b; ∂ϕ] / [∂g; ∂h] and of the tangents of the per-instance block.
+template <int FAMILY, bool JVP, int NVMAX, int NSMAX, class GEN, int NB = kNB, bool SPLIT = false>
 __device__ __forceinline__ void sens_instances(const WgSensArgs& W) {
   constexpr bool NL = FAMILY == MCPX_FAMILY_NONLINEAR;
+  static_assert(!SPLIT || !NL, "generated modules have no split θ");
   __shared__ SolveShared<NVMAX, NSMAX, false, false, NB> S;  // several right-hand sides: the HBM LU
   const SensArgs& a = W.s;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -285,7 +289,10 @@ __device__ __forceinline__ void sens_instances(const WgSensArgs& W) {
     const int64_t inst = S.sc.inst;
     __syncthreads();
     if (inst >= W.batch) break;  // every workgroup reaches this exit
-    const double* __restrict__ th = a.theta + inst * a.theta_ld;
+    const double* th_;
+    if constexpr (SPLIT) th_ = a.theta;
+    else th_ = a.theta + inst * a.theta_ld;
+    const double* __restrict__ th = th_;
     const bool has_gs = a.gs || a.ga_s != 0.0;  // else ∂l/∂s = ZeroTangent
     auto gs_at = [&](int k) { return affine_ct(a.ga_s, zs[nr + k], a.gs ? a.gs + inst * m + k : nullptr); };
 
@@ -333,7 +340,8 @@ __device__ __forceinline__ void sens_instances(const WgSensArgs& W) {
               v = jac<FAMILY, GEN>(th, blk, zs, n, m, r, j);
             } else {
               const double* d = a.theta_dot + (inst * K + c0 + (j - ns)) * p;
-              v = -(NL ? dtheta_row_nl<GEN>(dth, d, nr, r) : dtheta_row_aff<FAMILY>(d, zs, n, m, r));
+              if constexpr (SPLIT) v = -dvar_row<FAMILY>(d, r, n, m);
+              else v = -(NL ? dtheta_row_nl<GEN>(dth, d, nr, r) : dtheta_row_aff<FAMILY>(d, zs, n, m, r));
             }
           } else {
             if (j < n) {
@@ -376,8 +384,15 @@ __device__ __forceinline__ void sens_instances(const WgSensArgs& W) {
         lam[i] = u;
       }
       __syncthreads();
-      for (int64_t t = tid; t < p; t += WG)
-        a.out[inst * p + t] = ok_all ? dtheta_entry<FAMILY, GEN>(t, lam, zs, dth, n, m) : __builtin_nan("");
+      if constexpr (SPLIT) {  // t ∈ [shared_dim, shared_dim + n + m) of the family's θ′ only
+        const int64_t t0 = (int64_t)n * n + (FAMILY == MCPX_FAMILY_QP ? 1 : 2) * (int64_t)n * m +
+                           (FAMILY == MCPX_FAMILY_QP ? 0 : (int64_t)m * m);
+        for (int t = tid; t < nr; t += WG)
+          a.out[inst * nr + t] = ok_all ? dtheta_entry<FAMILY, GEN>(t0 + t, lam, zs, dth, n, m) : __builtin_nan("");
+      } else {
+        for (int64_t t = tid; t < p; t += WG)
+          a.out[inst * p + t] = ok_all ? dtheta_entry<FAMILY, GEN>(t, lam, zs, dth, n, m) : __builtin_nan("");
+      }
     }
     if (a.status && tid == 0) a.status[inst] = ok_all ? 0 : 1;
     __syncthreads();
