@@ -396,8 +396,7 @@ int mcpx_jvp_batch_device(const mcpx_desc* desc, const double* theta, const doub
  * var_dim doubles per instance; num_devices and MCPX_HOST_SHARDS are those of mcpx_vjp_batch.
  * Errors, the empty batch, the size limit (MCPX_MAX_WG_KKT_DIM) and MCPX_ENODEV are as in the
  * full-θ sensitivity calls; MCPX_FAMILY_NONLINEAR: MCPX_EINVAL.  (No mcpx_cond_batch on a split
- * θ, and no reduced Σ_b ∂shared: a caller who needs ∂M or ∂A has a θ-dependent matrix block and
- * no split.)  Added under 2.2.0 without a version step, as the shared solve entries. */
+ * θ.)  Added under 2.2.0 without a version step, as the shared solve entries. */
 int mcpx_vjp_batch_shared(const mcpx_desc* desc, const double* theta_shared, const double* x, const double* y,
                           const double* s, const double* gx, const double* gy, const double* gs,
                           int num_devices, double* dvar, int32_t* status);
@@ -415,6 +414,56 @@ int mcpx_solve_vjp_batch_shared_device(const mcpx_desc* desc, const double* thet
                                        const double* s0, const mcpx_params* prm, const mcpx_out* out,
                                        const mcpx_cotangent* ct, double* dvar, int32_t* vjp_status,
                                        void* stream);
+
+/* The reduced gradient of the SHARED block of a shared-matrix batch: Σ_b of the matrix blocks of
+ * the full pullback record, for a caller whose matrices are weights shared by every instance of
+ * the batch (an optimisation layer: ∂weights = Σ_b ∂θ′_b over the shared block).  The call runs
+ * mcpx_vjp_batch_shared[_device] and contracts its λ (= dvar) with the iterate over the batch
+ * axis on the matrix cores; no per-instance record of the matrix block is formed or stored.
+ *   skip     [B] or NULL: instance b is left out of the sum when skip[b] != 0 (e.g. the solve's
+ *            status, to leave out failed solves);
+ *   dshared  [mcpx_theta_shared_dim], the layout of the shared block;
+ *   used     the number of instances summed;
+ *   dvar     [B × var_dim] or NULL, status [B] or NULL: exactly what mcpx_vjp_batch_shared[_device]
+ *            returns for the same inputs (skip does not touch them).
+ * Contract — one defined bit pattern:
+ *   chunks     instance b of the whole call belongs to chunk c = b / MCPX_REDUCE_CHUNK; the last
+ *              chunk may be short.
+ *   inclusion  b is included when (skip == NULL or skip[b] == 0) and its pullback status is 0.
+ *              For an excluded instance every multiplication operand taken from it (x, y, λ) is
+ *              replaced by +0.0; the chain still runs.  A NaN row of a singular ∇F_z, or the
+ *              non-finite iterate of a failed solve, therefore never reaches the sum.  Such a
+ *              step, fma(+0.0, +0.0, acc), returns acc except that it turns an accumulator of
+ *              −0.0 into +0.0; an implementation may run further steps of this kind (the kernels
+ *              pad a short chunk with them).  Neither can show in dshared: the fold starts from
+ *              +0.0, and +0.0 + (−0.0) = +0.0 + (+0.0).
+ *   entries    per chunk and entry: acc = +0.0, instances ascending, every step an fma.
+ *              QP, λy = dvar[b][:m] (∂b), λx = dvar[b][m:] (∂ϕ):
+ *                ∂M_ij  acc = fma(−λx_i, x_j, acc)
+ *                ∂A_kj  acc = fma(−λy_k, x_j, acc), then acc = fma(λx_j, y_k, acc)
+ *              (with B = 1 the full record's entries).  Affine, ∂g = dvar[b][:n], ∂h = dvar[b][n:]:
+ *                ∂P_ij  fma(∂g_i, x_j, acc)     ∂Q_ik  fma(∂g_i, y_k, acc)
+ *                ∂R_kj  fma(∂h_k, x_j, acc)     ∂S_kq  fma(∂h_k, y_q, acc)
+ *   fold       dshared = ((+0.0 + P₀) + P₁) + P₂ …, the chunk partials in ascending chunk order,
+ *              plain additions.
+ * The bits do not depend on num_devices, MCPX_HOST_SHARDS, MCPX_HOST_CHUNK, the launch geometry,
+ * or which kernel produced λ.  The host call cuts its shards at multiples of MCPX_REDUCE_CHUNK
+ * (for this entry only), uploads the shared block once per device, and folds the shards' chunk
+ * partials in global chunk order.  Sizes: every (n, m) of the split pullback, m = 0 included.
+ * Errors and MCPX_ENODEV as mcpx_vjp_batch_shared*; NULL dshared or used: MCPX_EINVAL; an empty
+ * batch gives dshared = +0.0 throughout and used = 0 (the host call then needs no device).
+ * Added under 2.2.0 without a version step, as the other shared entries. */
+#define MCPX_REDUCE_CHUNK 64
+int mcpx_vjp_batch_shared_reduce(const mcpx_desc* desc, const double* theta_shared, const double* x,
+                                 const double* y, const double* s, const double* gx, const double* gy,
+                                 const double* gs, const uint8_t* skip, int num_devices, double* dshared,
+                                 int64_t* used, double* dvar, int32_t* status);
+/* The same on device buffers of the current device (dshared and used included), enqueued on
+ * `stream`; with dvar (status) NULL the pullback writes into a block of the library's own. */
+int mcpx_vjp_batch_shared_reduce_device(const mcpx_desc* desc, const double* theta_shared, const double* x,
+                                        const double* y, const double* s, const double* gx, const double* gy,
+                                        const double* gs, const uint8_t* skip, double* dshared, int64_t* used,
+                                        double* dvar, int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Nonlinear G/H — MCPX_FAMILY_NONLINEAR (BASELINE C4: games, src/game.jl).

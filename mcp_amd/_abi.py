@@ -104,6 +104,17 @@ class Cotangent(C.Structure):
     ]
 
 
+# mcpx_vjp_batch_shared_reduce[_device]: the reduced gradient of a shared-matrix batch's matrix block.
+# REDUCE_CHUNK (MCPX_REDUCE_CHUNK) is part of the result's contract: instances are summed in
+# chunks of this many, the chunk partials then added in ascending order.
+REDUCE_CHUNK = 64
+_P = C.c_void_p
+# (desc, theta_shared, x, y, s, gx, gy, gs, skip, num_devices, dshared, used, dvar, status)
+VJP_SHARED_REDUCE_ARGTYPES = [C.POINTER(Desc), _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P]
+# (desc, theta_shared, x, y, s, gx, gy, gs, skip, dshared, used, dvar, status, stream)
+VJP_SHARED_REDUCE_DEVICE_ARGTYPES = [C.POINTER(Desc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]
+
+
 def make_params(tol=1e-4, max_inner_iters=20, max_outer_iters=50, tightening_rate=0.1,
                 loosening_rate=0.5, min_stepsize=1e-4, tau=0.995, decay=0.5,
                 linear_solver="reduced", kernel="auto") -> Params:

@@ -35,7 +35,8 @@ EXPORTS = ("mcpx_version", "mcpx_last_error", "mcpx_default_params", "mcpx_theta
            "mcpx_debug_canary_violations", "mcpx_theta_shared_dim", "mcpx_theta_var_dim",
            "mcpx_solve_batch_shared", "mcpx_solve_batch_shared_device", "mcpx_vjp_batch_shared",
            "mcpx_vjp_batch_shared_device", "mcpx_jvp_batch_shared", "mcpx_jvp_batch_shared_device",
-           "mcpx_solve_vjp_batch_shared_device")
+           "mcpx_solve_vjp_batch_shared_device", "mcpx_vjp_batch_shared_reduce",
+           "mcpx_vjp_batch_shared_reduce_device")
 
 
 ABI_MAJOR = 2  # include/mcpx.h MCPX_VERSION / 10000
@@ -101,6 +102,10 @@ def lib():
     L.mcpx_solve_vjp_batch_shared_device.argtypes = [C.POINTER(_abi.Desc), P, P, P, P, P, C.POINTER(_abi.Params),
                                                      C.POINTER(_abi.Out), C.POINTER(_abi.Cotangent), P, P,
                                                      C.c_void_p]
+    L.mcpx_vjp_batch_shared_reduce.restype = C.c_int
+    L.mcpx_vjp_batch_shared_reduce.argtypes = _abi.VJP_SHARED_REDUCE_ARGTYPES
+    L.mcpx_vjp_batch_shared_reduce_device.restype = C.c_int
+    L.mcpx_vjp_batch_shared_reduce_device.argtypes = _abi.VJP_SHARED_REDUCE_DEVICE_ARGTYPES
     I32P = C.POINTER(C.c_int32)
     L.mcpx_module_load.restype = C.c_int
     L.mcpx_module_load.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]

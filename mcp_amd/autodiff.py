@@ -263,6 +263,108 @@ def _autograd_fn():
 _FN = None
 
 
+class _BackwardRecord:
+    """What the backward pass of solve_shared_torch leaves behind.  It references none of the
+    autograd outputs, so the node that holds it closes no reference cycle with them."""
+
+    __slots__ = ("out", "used", "sensitivity_status")
+
+    def __init__(self):
+        self.out = self.used = self.sensitivity_status = None
+
+
+@dataclass
+class SharedSolution:
+    """What :func:`solve_shared_torch` returns: the iterate (differentiable w.r.t. theta_shared and
+    theta_var), the solve's per-instance status, every output of the solve (`out`, the dict of
+    solve_batch_shared_device), and after a backward pass `used`: a one-element int64 device
+    tensor, the number of instances that entered theta_shared's gradient, with
+    `sensitivity_status` (B,), the pullback's status."""
+
+    x: Any
+    y: Any
+    s: Any
+    status: Any
+    record: Any = None
+
+    @property
+    def out(self):
+        return self.record.out
+
+    @property
+    def used(self):
+        return self.record.used
+
+    @property
+    def sensitivity_status(self):
+        return self.record.sensitivity_status
+
+
+def _shared_autograd_fn():
+    import torch
+
+    class _SolveSharedFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, theta_shared, theta_var, rec, family, n, m, skip_failed, params):
+            from .batch import solve_batch_shared_device
+
+            out = solve_batch_shared_device(family, n, m, theta_shared.detach().contiguous(),
+                                            theta_var.detach().contiguous(), **params)
+            ctx.save_for_backward(theta_shared.detach())
+            # the node keeps the record (and through it the solve's own buffers), never the
+            # SharedSolution, whose x / y / s are this node's outputs
+            ctx.rec, ctx.cfg = rec, (family, n, m, skip_failed)
+            rec.out = out
+            ctx.mark_non_differentiable(out["status"])
+            return out["x"].clone(), out["y"].clone(), out["s"].clone(), out["status"]
+
+        @staticmethod
+        def backward(ctx, gx, gy, gs, _gstatus):
+            from .batch import vjp_batch_shared_reduce_device
+
+            (theta_shared,) = ctx.saved_tensors
+            family, n, m, skip_failed = ctx.cfg
+            rec, out = ctx.rec, ctx.rec.out
+            B = out["status"].shape[0]
+            f = lambda t: None if t is None else t.to(torch.float64).reshape(B, -1).contiguous()
+            skip = (out["status"] != 0).to(torch.uint8) if skip_failed else None
+            dshared, used, dvar, st = vjp_batch_shared_reduce_device(
+                family, n, m, theta_shared.contiguous(), out["x"], out["y"], out["s"], f(gx), f(gy), f(gs),
+                skip=skip)
+            rec.used, rec.sensitivity_status = used, st
+            return dshared.reshape(theta_shared.shape), dvar, None, None, None, None, None, None
+
+    return _SolveSharedFn
+
+
+_SHARED_FN = None
+
+
+def solve_shared_torch(family: int, n: int, m: int, theta_shared, theta_var, *, skip_failed: bool = True,
+                       **params) -> SharedSolution:
+    """Differentiable solve of a shared-matrix batch whose matrices are trainable weights (an
+    optimisation layer): theta_shared the (shared_dim,) matrix block [vec(M); vec(A)] (affine:
+    [P; Q; R; S]) of every instance, theta_var the (B, n + m) per-instance block, float64 HIP
+    tensors.  Forward: solve_batch_shared_device (`params`: its keyword arguments).  Backward: one
+    vjp_batch_shared_reduce_device call at the returned iterate — theta_shared.grad is Σ_b of the
+    matrix blocks of the per-instance pullbacks, with one defined bit pattern (include/mcpx.h),
+    theta_var.grad the rows of the split pullback.  skip_failed: instances whose solve failed stay
+    out of theta_shared's gradient (their theta_var rows are the pullback's, as they are).
+    Instances whose ∇F_z is singular are always left out.  The families' own θ′ only: routing
+    through PrimalDualMCP / ThetaMap needs batch-shared user parameters."""
+    global _SHARED_FN
+    if not (_is_torch(theta_shared) and theta_shared.is_cuda and _is_torch(theta_var) and theta_var.is_cuda):
+        raise ValueError("solve_shared_torch needs HIP (cuda) tensors theta_shared and theta_var")
+    if theta_var.dim() != 2 or theta_var.shape[1] != n + m:
+        raise ValueError("theta_var must be a (B, n + m) tensor")
+    if _SHARED_FN is None:
+        _SHARED_FN = _shared_autograd_fn()
+    rec = _BackwardRecord()
+    x, y, s, status = _SHARED_FN.apply(theta_shared, theta_var, rec, int(family), int(n), int(m), bool(skip_failed),
+                                       dict(params))
+    return SharedSolution(x, y, s, status, rec)
+
+
 def solve_torch(mcp, θ, *, solver_type=None, **kwargs):
     """Differentiable batched solve on device: θ a (B, p) float64 HIP tensor
     (requires_grad allowed) → (x, y, s, status) with x, y, s differentiable

@@ -590,3 +590,71 @@ def solve_vjp_batch_shared_device(family: int, n: int, m: int, theta_shared, the
                                                    C.byref(prm), C.byref(o), C.byref(cot), _dev_f64(dvar, "dvar"),
                                                    dp(status), C.c_void_p(st.cuda_stream)))
     return out, dvar, status
+
+
+# ---------------------------------------------------------------------------
+# the reduced gradient of the matrix block of a shared-matrix batch (include/mcpx.h
+# mcpx_vjp_batch_shared_reduce*): Σ_b ∂shared for matrices that are weights shared by the batch
+
+
+def vjp_batch_shared_reduce(family: int, n: int, m: int, theta_shared, x, y, s, gx=None, gy=None, gs=None,
+                            skip=None, num_devices: int = 0, want_dvar: bool = True) -> tuple:
+    """vjp_batch_shared plus the gradient of the shared block summed over the batch
+    (mcpx_vjp_batch_shared_reduce).  `skip` (B,): instances with a nonzero entry are left out of the
+    sum, as are those whose pullback status is 1.  Returns (dshared (shared_dim,) in the layout of
+    theta_shared, used: the number of instances summed, dvar (B, n + m) or None, status (B,)); dvar
+    and status are vjp_batch_shared's.  dshared has one defined bit pattern (chunks of
+    _abi.REDUCE_CHUNK instances, include/mcpx.h), whatever the devices and shards."""
+    theta_shared = _host_shared(family, n, m, theta_shared)
+    B = _batch_of(np.atleast_2d(np.asarray(x)), np.atleast_2d(np.asarray(y)), n, m)
+    dv = _abi.theta_var_dim(family, n, m)
+    x, y, s = _host_f64(x, (B, n)), _host_f64(y, (B, m)), _host_f64(s, (B, m))
+    gx, gy, gs = _host_f64(gx, (B, n)), _host_f64(gy, (B, m)), _host_f64(gs, (B, m))
+    if skip is not None:
+        skip = np.ascontiguousarray(np.broadcast_to(np.asarray(skip) != 0, (B,)), dtype=np.uint8)
+    dshared = np.empty(theta_shared.size)
+    used = np.zeros(1, np.int64)
+    dvar = np.empty((B, dv)) if want_dvar else None
+    st = np.empty(B, np.int32)
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(dv))
+    check(lib().mcpx_vjp_batch_shared_reduce(C.byref(desc), _ptr(theta_shared), _ptr(x), _ptr(y), _ptr(s), _ptr(gx),
+                                             _ptr(gy), _ptr(gs), _ptr(skip), int(num_devices), _ptr(dshared),
+                                             _ptr(used), _ptr(dvar), _ptr(st)))
+    return dshared, int(used[0]), dvar, st
+
+
+def vjp_batch_shared_reduce_device(family: int, n: int, m: int, theta_shared, x, y, s, gx=None, gy=None, gs=None,
+                                   skip=None, dshared=None, used=None, dvar=None, status=None,
+                                   want_dvar: bool = True, stream=None):
+    """Device-tensor form, enqueued on the current stream (no sync): `skip` a (B,) uint8 / bool
+    device tensor or None.  Returns (dshared (shared_dim,), used (1,) int64, dvar (B, n + m) or
+    None, status (B,) int32) tensors.  want_dvar=False with dvar=None: the pullback's λ stays in a
+    block of the library's own and None is returned for it."""
+    import torch
+
+    sh = _dev_shared(family, n, m, theta_shared)
+    B = _batch_of(x, y, n, m)
+    dv = _abi.theta_var_dim(family, n, m)
+    dev = theta_shared.device
+    if dshared is None:
+        dshared = torch.empty(theta_shared.numel(), dtype=torch.float64, device=dev)
+    if used is None:
+        used = torch.empty(1, dtype=torch.int64, device=dev)
+    if dvar is None and want_dvar:
+        dvar = torch.empty(B, dv, dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+    if skip is not None:
+        if skip.dtype == torch.bool:
+            skip = skip.view(torch.uint8)
+        if not (skip.is_cuda and skip.dtype == torch.uint8 and skip.is_contiguous() and skip.numel() == B):
+            raise ValueError("skip must be a contiguous (B,) uint8 or bool device tensor")
+    if not (used.is_cuda and used.dtype == torch.int64 and used.numel() == 1):
+        raise ValueError("used must be a one-element int64 device tensor")
+    ptrs = [_dev_f64(t, k) for t, k in ((x, "x"), (y, "y"), (s, "s"), (gx, "gx"), (gy, "gy"), (gs, "gs"))]
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(dv))
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    check(lib().mcpx_vjp_batch_shared_reduce_device(
+        C.byref(desc), sh, *ptrs, None if skip is None else skip.data_ptr(), _dev_f64(dshared, "dshared"),
+        used.data_ptr(), _dev_f64(dvar, "dvar"), status.data_ptr(), C.c_void_p(st.cuda_stream)))
+    return dshared, used, dvar, status

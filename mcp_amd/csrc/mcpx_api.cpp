@@ -655,17 +655,20 @@ int host_shards(int num_devices, int64_t batch) {
 
 // Runs fn(device, b0, nb) over the contiguous shards of a host-buffer call: shard g (device
 // g mod devices) gets ⌊B/G⌋ instances (+1 for g < B mod G).  One host thread per shard; a
-// single shard runs on the caller's thread.
+// single shard runs on the caller's thread.  `unit` > 1 (mcpx_vjp_batch_shared_reduce): the
+// shards are cut at multiples of `unit` instances, the units dealt out as the instances are.
 template <class Fn>
-int run_shards(int num_devices, int64_t batch, Fn&& fn) {
+int run_shards(int num_devices, int64_t batch, Fn&& fn, int64_t unit = 1) {
   const int avail = mcpx_device_count();
   if (avail < 1) return fail(MCPX_ENODEV, "no HIP device visible");
+  const int64_t units = (batch + unit - 1) / unit;
   if (num_devices <= 0 || num_devices > avail) num_devices = avail;
-  if ((int64_t)num_devices > batch) num_devices = (int)batch;
-  const int devs = num_devices, shards = host_shards(devs, batch);
+  if ((int64_t)num_devices > units) num_devices = (int)units;
+  const int devs = num_devices, shards = host_shards(devs, units);
   if (shards == 1) return fn(0, (int64_t)0, batch);
   std::vector<int64_t> start(shards + 1, 0);
-  for (int g = 0; g < shards; ++g) start[g + 1] = start[g] + batch / shards + (g < batch % shards ? 1 : 0);
+  for (int g = 0; g < shards; ++g)
+    start[g + 1] = std::min(batch, (start[g] + unit - 1) / unit * unit + unit * (units / shards + (g < units % shards ? 1 : 0)));
   std::vector<int> rcs(shards, 0);
   std::vector<std::string> errs(shards);
   std::vector<std::thread> th;
@@ -905,6 +908,189 @@ mcpx::SensArgs sens_args(const double* theta, const double* x, const double* y, 
   a.out = out;
   a.status = status;
   return a;
+}
+
+// ---- the reduced gradient of the shared block (mcpx_vjp_batch_shared_reduce*) --------------
+
+// Bytes of chunk partials one launch of shared_reduce_partial may leave behind: past it the
+// chunks go through the block in groups, each folded (or copied out) before the next
+// overwrites it, so the scratch does not grow with B · shared_dim.
+// MCPX_REDUCE_CAP_KB (test knob, ≥ 1): the cap in KiB, so that a small batch runs in groups.
+int64_t reduce_partial_cap() {
+  const char* e = std::getenv("MCPX_REDUCE_CAP_KB");
+  const long long v = e ? std::atoll(e) : 32ll << 10;
+  return (int64_t)(v < 1 ? 1 : v) << 10;
+}
+
+// The checks of the reduce entries after prepare_sens (dvar and status may be NULL).
+int reduce_inputs_ok(const mcpx_desc* d, const mcpx::SensArgs& a, const double* dshared, const int64_t* used) {
+  if (!dshared || !used) return fail(MCPX_EINVAL, "dshared and used must be non-NULL");
+  if (d->batch == 0) return MCPX_OK;
+  if (!a.theta) return fail(MCPX_EINVAL, "theta_shared must be non-NULL");
+  if ((d->n > 0 && !a.x) || (d->m > 0 && (!a.y || !a.s)))
+    return fail(MCPX_EINVAL, "solution arrays x/y/s must be non-NULL");
+  return MCPX_OK;
+}
+
+// The split pullback of `a` (device pointers; a.out / a.status NULL: into a pool block), then
+// the chunk partials of Σ_b ∂shared, all on `st`.  d->batch instances that start a chunk.
+// hpart == NULL: folded on the device into dshared / used (device pointers).  Otherwise the
+// partials and counts of every chunk are copied to hpart [chunks × ds] / hcount [chunks] (host),
+// for the caller to fold across shards.
+int launch_shared_reduce(const mcpx_desc* d, mcpx::SensArgs a, const SensPlan& plan, const uint8_t* skip,
+                         double* dshared, int64_t* used, double* hpart, int64_t* hcount, hipStream_t st) {
+  const int n = d->n, m = d->m;
+  const int64_t B = d->batch, ds = mcpx_theta_shared_dim(d->family, n, m);
+  const int64_t nch = (B + MCPX_REDUCE_CHUNK - 1) / MCPX_REDUCE_CHUNK;
+  const int64_t group = std::max<int64_t>(1, std::min(nch, reduce_partial_cap() / (std::max<int64_t>(ds, 1) * 8)));
+  AsyncBuf<double> own_dvar, part;
+  AsyncBuf<int32_t> own_status;
+  AsyncBuf<int64_t> count;
+  if (!a.out) {
+    HIP_TRY(own_dvar.alloc((size_t)B * (n + m), st));
+    a.out = own_dvar.p;
+  }
+  if (!a.status) {
+    HIP_TRY(own_status.alloc((size_t)B, st));
+    a.status = own_status.p;
+  }
+  HIP_TRY(part.alloc((size_t)(group * std::max<int64_t>(ds, 1)), st));
+  HIP_TRY(count.alloc((size_t)group, st));
+  if (const int rc = launch_sens(false, d, a, plan, st)) return rc;
+  mcpx::ReduceArgs r{};
+  r.x = a.x;
+  r.y = a.y;
+  r.dvar = a.out;
+  r.status = a.status;
+  r.skip = skip;
+  r.part = part.p;
+  r.count = count.p;
+  r.batch = B;
+  r.ds = ds;
+  r.n = n;
+  r.m = m;
+  r.family = d->family;
+  for (int64_t c0 = 0; c0 < nch; c0 += group) {
+    const int64_t nc = std::min(group, nch - c0);
+    r.chunk0 = c0;
+    HIP_TRY(mcpx::launch_shared_reduce_partial(r, nc, st));
+    if (!hpart) {
+      HIP_TRY(mcpx::launch_shared_reduce_fold(part.p, count.p, nc, ds, c0 == 0, dshared, used, st));
+    } else {  // stream-ordered: both copies are done before the next group's kernel starts
+      if (ds > 0)
+        HIP_TRY(hipMemcpyAsync(hpart + c0 * ds, part.p, sizeof(double) * (size_t)(nc * ds), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(hcount + c0, count.p, sizeof(int64_t) * (size_t)nc, hipMemcpyDeviceToHost, st));
+    }
+  }
+  return MCPX_OK;
+}
+
+// What the reduce entries take beyond a split pullback's SensArgs.
+struct ReduceCall {
+  const uint8_t* skip;
+  double* dshared;
+  int64_t* used;
+};
+
+int shared_reduce_device(const mcpx_desc* d, mcpx::SensArgs a, const ReduceCall& c, void* stream) {
+  SensPlan plan;
+  int rc;
+  if ((rc = prepare_sens(d, &a, &plan, kVjp, nullptr, true))) return rc;
+  if ((rc = reduce_inputs_ok(d, a, c.dshared, c.used))) return rc;
+  int dev = 0;
+  if ((rc = current_device(&dev))) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  if (d->batch == 0) {  // the empty sum: all bits zero is +0.0 and 0
+    const int64_t ds = mcpx_theta_shared_dim(d->family, d->n, d->m);
+    if (ds > 0) HIP_TRY(hipMemsetAsync(c.dshared, 0, sizeof(double) * (size_t)ds, st));
+    HIP_TRY(hipMemsetAsync(c.used, 0, sizeof(int64_t), st));
+    return MCPX_OK;
+  }
+  // empty x/y blocks (n = 0 or m = 0) still need a valid base pointer
+  if (!a.x) a.x = a.theta;
+  if (!a.y) a.y = a.theta;
+  if (!a.s) a.s = a.theta;
+  return launch_shared_reduce(d, a, plan, c.skip, c.dshared, c.used, nullptr, nullptr, st);
+}
+
+// One device's share [b0, b0 + nb) of the host call, b0 a multiple of MCPX_REDUCE_CHUNK: the
+// chunk partials and counts of the shard into hpart / hcount at its global chunk index.
+int shared_reduce_shard(int dev, const mcpx_desc* d, const mcpx::SensArgs& a, const SensPlan& plan,
+                        const ReduceCall& c, double* hpart, int64_t* hcount, int64_t b0, int64_t nb) {
+  HIP_TRY(hipSetDevice(dev));
+  int rc = check_device(dev);
+  if (rc) return rc;
+  const int n = d->n, m = d->m;
+  const int64_t ds = mcpx_theta_shared_dim(d->family, n, m);
+  DevBuf<double> th, dx, dy, dsl, dgx, dgy, dgs, dout;
+  DevBuf<int32_t> dst;
+  DevBuf<uint8_t> dskip;
+  auto up = [&](DevBuf<double>& b, const double* h, size_t per) -> hipError_t {
+    if (!h || !per) return hipSuccess;
+    hipError_t e = b.alloc((size_t)nb * per);
+    return e != hipSuccess ? e : hipMemcpy(b.p, h + b0 * per, sizeof(double) * nb * per, hipMemcpyHostToDevice);
+  };
+  HIP_TRY(th.alloc((size_t)std::max<int64_t>(ds, 1)));
+  if (ds > 0) HIP_TRY(hipMemcpy(th.p, a.theta, sizeof(double) * (size_t)ds, hipMemcpyHostToDevice));
+  HIP_TRY(up(dx, a.x, n)); HIP_TRY(up(dy, a.y, m)); HIP_TRY(up(dsl, a.s, m));
+  HIP_TRY(up(dgx, a.gx, n)); HIP_TRY(up(dgy, a.gy, m)); HIP_TRY(up(dgs, a.gs, m));
+  if (c.skip) {
+    HIP_TRY(dskip.alloc((size_t)nb));
+    HIP_TRY(hipMemcpy(dskip.p, c.skip + b0, (size_t)nb, hipMemcpyHostToDevice));
+  }
+  if (a.out) HIP_TRY(dout.alloc((size_t)nb * (n + m)));
+  if (a.status) HIP_TRY(dst.alloc((size_t)nb));
+  mcpx_desc dd = *d;
+  dd.batch = nb;
+  mcpx::SensArgs da = a;  // the same call on the shard's device buffers
+  da.theta = th.p;
+  da.x = dx.p ? dx.p : th.p;
+  da.y = dy.p ? dy.p : th.p;
+  da.s = dsl.p ? dsl.p : th.p;
+  da.gx = dgx.p;
+  da.gy = dgy.p;
+  da.gs = dgs.p;
+  da.out = dout.p;
+  da.status = dst.p;
+  const int64_t c0 = b0 / MCPX_REDUCE_CHUNK;
+  rc = launch_shared_reduce(&dd, da, plan, dskip.p, nullptr, nullptr, hpart + c0 * ds, hcount + c0, nullptr);
+  if (rc) {
+    (void)hipDeviceSynchronize();  // nothing may still run on the buffers freed on return
+    return rc;
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  if (a.out) HIP_TRY(hipMemcpy(a.out + b0 * (n + m), dout.p, sizeof(double) * nb * (n + m), hipMemcpyDeviceToHost));
+  if (a.status) HIP_TRY(hipMemcpy(a.status + b0, dst.p, sizeof(int32_t) * nb, hipMemcpyDeviceToHost));
+  return MCPX_OK;
+}
+
+int shared_reduce_host(const mcpx_desc* d, mcpx::SensArgs a, const ReduceCall& c, int num_devices) {
+  SensPlan plan;
+  int rc;
+  if ((rc = prepare_sens(d, &a, &plan, kVjp, nullptr, true))) return rc;
+  if ((rc = reduce_inputs_ok(d, a, c.dshared, c.used))) return rc;
+  const int64_t ds = mcpx_theta_shared_dim(d->family, d->n, d->m);
+  const int64_t nch = (d->batch + MCPX_REDUCE_CHUNK - 1) / MCPX_REDUCE_CHUNK;
+  std::vector<double> hpart;
+  std::vector<int64_t> hcount((size_t)nch, 0);
+  if (nch > 0) {
+    if (mcpx_device_count() < 1) return fail(MCPX_ENODEV, "no HIP device visible");
+    hpart.resize((size_t)(nch * ds));
+    rc = run_shards(num_devices, d->batch, [&](int dev, int64_t b0, int64_t nb) {
+      return shared_reduce_shard(dev, d, a, plan, c, hpart.data(), hcount.data(), b0, nb);
+    }, MCPX_REDUCE_CHUNK);
+    if (rc) return rc;
+  }
+  // the fold of shared_reduce_fold, over every shard's chunks in global order
+  int64_t u = 0;
+  for (int64_t e = 0; e < ds; ++e) c.dshared[e] = 0.0;
+  for (int64_t k = 0; k < nch; ++k) {
+    const double* p = hpart.data() + k * ds;
+    for (int64_t e = 0; e < ds; ++e) c.dshared[e] = c.dshared[e] + p[e];
+    u += hcount[(size_t)k];
+  }
+  *c.used = u;
+  return MCPX_OK;
 }
 
 // mcpx_solve_batch_device / mcpx_solve_batch_module_device (mod = nullptr: QP / affine kernels).
@@ -1179,6 +1365,28 @@ int mcpx_vjp_batch_shared(const mcpx_desc* d, const double* theta_shared, const 
   a.gy = gy;
   a.gs = gs;
   return sens_host(kVjp, nullptr, d, a, num_devices, true);
+}
+
+int mcpx_vjp_batch_shared_reduce_device(const mcpx_desc* d, const double* theta_shared, const double* x,
+                                        const double* y, const double* s, const double* gx, const double* gy,
+                                        const double* gs, const uint8_t* skip, double* dshared, int64_t* used,
+                                        double* dvar, int32_t* status, void* stream) {
+  mcpx::SensArgs a = sens_args(theta_shared, x, y, s, dvar, status);
+  a.gx = gx;
+  a.gy = gy;
+  a.gs = gs;
+  return shared_reduce_device(d, a, ReduceCall{skip, dshared, used}, stream);
+}
+
+int mcpx_vjp_batch_shared_reduce(const mcpx_desc* d, const double* theta_shared, const double* x, const double* y,
+                                 const double* s, const double* gx, const double* gy, const double* gs,
+                                 const uint8_t* skip, int num_devices, double* dshared, int64_t* used, double* dvar,
+                                 int32_t* status) {
+  mcpx::SensArgs a = sens_args(theta_shared, x, y, s, dvar, status);
+  a.gx = gx;
+  a.gy = gy;
+  a.gs = gs;
+  return shared_reduce_host(d, a, ReduceCall{skip, dshared, used}, num_devices);
 }
 
 int mcpx_jvp_batch_shared_device(const mcpx_desc* d, const double* theta_shared, const double* x, const double* y,

@@ -63,4 +63,26 @@ hipError_t launch_jvp(int nmax, const SensArgs& a, int64_t batch, hipStream_t st
 hipError_t launch_vjp_shared(int nmax, const SensArgs& a, int64_t batch, hipStream_t st);
 hipError_t launch_jvp_shared(int nmax, const SensArgs& a, int64_t batch, hipStream_t st);
 
+// The reduced gradient of the shared block (mcpx_vjp_batch_shared_reduce*, shared_reduce.hip).
+struct ReduceArgs {
+  const double* x;        // [B*n]
+  const double* y;        // [B*m]
+  const double* dvar;     // [B*(n+m)]: the split pullback's output (λ)
+  const int32_t* status;  // [B]: the split pullback's status
+  const uint8_t* skip;    // [B] or NULL
+  double* part;           // [chunks of the launch × ds]: the chunk partials
+  int64_t* count;         // [chunks of the launch]: included instances per chunk
+  int64_t batch;          // B: the arrays' instances; the last chunk may be short
+  int64_t chunk0;         // the launch's first chunk (of MCPX_REDUCE_CHUNK instances)
+  int64_t ds;             // mcpx_theta_shared_dim
+  int32_t n, m;
+  int32_t family;
+  int32_t pad_;
+};
+// Partials of chunks [a.chunk0, a.chunk0 + nchunks) into a.part / a.count.
+hipError_t launch_shared_reduce_partial(const ReduceArgs& a, int64_t nchunks, hipStream_t st);
+// dshared / used ← (first ? 0 : their value) + the partials / counts, chunks ascending.
+hipError_t launch_shared_reduce_fold(const double* part, const int64_t* count, int64_t nchunks, int64_t ds,
+                                     bool first, double* dshared, int64_t* used, hipStream_t st);
+
 }  // namespace mcpx
