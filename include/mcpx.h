@@ -62,7 +62,9 @@ extern "C" {
  * mcpx_solve_batch_shared_device) were added under 2.2.0 without a version step: no struct and no
  * existing function changed, so every 2.x caller keeps working; a caller that needs them looks
  * the symbols up.  The same holds for their sensitivities (mcpx_vjp_batch_shared[_device],
- * mcpx_jvp_batch_shared[_device], mcpx_solve_vjp_batch_shared_device). */
+ * mcpx_jvp_batch_shared[_device], mcpx_solve_vjp_batch_shared_device), the reduced gradient
+ * (mcpx_vjp_batch_shared_reduce[_device]), the tangents along the shared block
+ * (mcpx_jvp_batch_shared_dot[_device]) and the condition estimate (mcpx_cond_batch_shared[_device]). */
 
 /* error codes */
 #define MCPX_OK 0
@@ -395,8 +397,10 @@ int mcpx_jvp_batch_device(const mcpx_desc* desc, const double* theta, const doub
  * The host calls upload the shared block once per device and no per-instance θ, and bring back
  * var_dim doubles per instance; num_devices and MCPX_HOST_SHARDS are those of mcpx_vjp_batch.
  * Errors, the empty batch, the size limit (MCPX_MAX_WG_KKT_DIM) and MCPX_ENODEV are as in the
- * full-θ sensitivity calls; MCPX_FAMILY_NONLINEAR: MCPX_EINVAL.  (No mcpx_cond_batch on a split
- * θ.)  Added under 2.2.0 without a version step, as the shared solve entries. */
+ * full-θ sensitivity calls; MCPX_FAMILY_NONLINEAR: MCPX_EINVAL.  (The tangents of the shared
+ * block and the condition estimate on a split θ: mcpx_jvp_batch_shared_dot and
+ * mcpx_cond_batch_shared below.)  Added under 2.2.0 without a version step, as the shared solve
+ * entries. */
 int mcpx_vjp_batch_shared(const mcpx_desc* desc, const double* theta_shared, const double* x, const double* y,
                           const double* s, const double* gx, const double* gy, const double* gs,
                           int num_devices, double* dvar, int32_t* status);
@@ -414,6 +418,50 @@ int mcpx_solve_vjp_batch_shared_device(const mcpx_desc* desc, const double* thet
                                        const double* s0, const mcpx_params* prm, const mcpx_out* out,
                                        const mcpx_cotangent* ct, double* dvar, int32_t* vjp_status,
                                        void* stream);
+
+/* Forward mode along a direction of the SHARED block as well — the forward-mode twin of the
+ * reduced gradient below, for a caller who moves the shared weights (a line search over a weight
+ * update, a Gauss-Newton product, a forward-mode check of mcpx_vjp_batch_shared_reduce):
+ *     θ̇_{b,c} = [shared_dot_c ‖ var_dot_{b,c}],   c = 0 .. n_partials−1.
+ *   shared_dot [n_partials × mcpx_theta_shared_dim], dense, given ONCE for the batch: partial c
+ *              of every instance has the same matrix tangent.  Required (NULL with batch > 0 and
+ *              n_partials > 0: MCPX_EINVAL);
+ *   var_dot    [B × n_partials × var_dim] as in mcpx_jvp_batch_shared, or NULL = +0.0 tangents
+ *              of the per-instance block;
+ *   zdot, status as in mcpx_jvp_batch_shared.
+ * Contract: zdot and status are bit-identical to mcpx_jvp_batch[_device] on the materialised θ′
+ * and θ̇, for EVERY instance: the NaN rows and status 1 of a singular ∇F_z, and non-finite
+ * iterates too — the matrix-tangent chains of the right-hand side really run here
+ * (fma(±Ṁ_ij, x_j, acc) …: the x-block chain, the y-block chain, then the vector term), so the
+ * "outside the contract" clause of mcpx_jvp_batch_shared does not apply.  With var_dot NULL the
+ * last step still runs on +0.0 (QP: acc − (+0.0); affine: acc + (+0.0), which is not the
+ * identity on acc = −0.0).
+ * The caller allocates K·shared_dim + B·K·var_dim doubles of tangents in place of B·K·p.  The
+ * host call uploads the shared block and shared_dot once per device, sends the iterate (and
+ * var_dot, if given) per shard and brings back zdot; num_devices and MCPX_HOST_SHARDS are those
+ * of mcpx_jvp_batch.  Errors, the empty batch, MCPX_ENODEV, the size limit, the theta_ld ≥
+ * var_dim check, MCPX_FAMILY_NONLINEAR → MCPX_EINVAL and n_partials ≤ 0 (negative: MCPX_EINVAL;
+ * 0: status only, shared_dot not read) as in mcpx_jvp_batch_shared.  Added under 2.2.0 without a
+ * version step, as the other shared entries. */
+int mcpx_jvp_batch_shared_dot(const mcpx_desc* desc, const double* theta_shared, const double* x, const double* y,
+                              const double* s, int32_t n_partials, const double* shared_dot,
+                              const double* var_dot, int num_devices, double* zdot, int32_t* status);
+int mcpx_jvp_batch_shared_dot_device(const mcpx_desc* desc, const double* theta_shared, const double* x,
+                                     const double* y, const double* s, int32_t n_partials,
+                                     const double* shared_dot, const double* var_dot, double* zdot,
+                                     int32_t* status, void* stream);
+
+/* mcpx_cond_batch of a shared-matrix batch: ∇F_z reads nothing per instance from θ′, so the
+ * call takes the one matrix block.  rcond and status are bit-identical to
+ * mcpx_cond_batch[_device] on the materialised θ′ (the same workgroup kernels, reading every
+ * instance's rows of ∇F_z from theta_shared).  The host call uploads the shared block once per
+ * device and brings back one double per instance.  Errors as the other shared sensitivity
+ * entries.  Added under 2.2.0 without a version step. */
+int mcpx_cond_batch_shared(const mcpx_desc* desc, const double* theta_shared, const double* x, const double* y,
+                           const double* s, int num_devices, double* rcond, int32_t* status);
+int mcpx_cond_batch_shared_device(const mcpx_desc* desc, const double* theta_shared, const double* x,
+                                  const double* y, const double* s, double* rcond, int32_t* status,
+                                  void* stream);
 
 /* The reduced gradient of the SHARED block of a shared-matrix batch: Σ_b of the matrix blocks of
  * the full pullback record, for a caller whose matrices are weights shared by every instance of

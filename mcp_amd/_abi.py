@@ -114,6 +114,13 @@ VJP_SHARED_REDUCE_ARGTYPES = [C.POINTER(Desc), _P, _P, _P, _P, _P, _P, _P, _P, C
 # (desc, theta_shared, x, y, s, gx, gy, gs, skip, dshared, used, dvar, status, stream)
 VJP_SHARED_REDUCE_DEVICE_ARGTYPES = [C.POINTER(Desc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]
 
+# mcpx_jvp_batch_shared_dot[_device]: the tangents of a shared-matrix batch along a direction of the
+# shared block (given once for the batch) and of the per-instance block (or NULL)
+# (desc, theta_shared, x, y, s, n_partials, shared_dot, var_dot, num_devices, zdot, status)
+JVP_SHARED_DOT_ARGTYPES = [C.POINTER(Desc), _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int, _P, _P]
+# (desc, theta_shared, x, y, s, n_partials, shared_dot, var_dot, zdot, status, stream)
+JVP_SHARED_DOT_DEVICE_ARGTYPES = [C.POINTER(Desc), _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P]
+
 
 def make_params(tol=1e-4, max_inner_iters=20, max_outer_iters=50, tightening_rate=0.1,
                 loosening_rate=0.5, min_stepsize=1e-4, tau=0.995, decay=0.5,

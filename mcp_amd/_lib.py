@@ -36,7 +36,8 @@ EXPORTS = ("mcpx_version", "mcpx_last_error", "mcpx_default_params", "mcpx_theta
            "mcpx_solve_batch_shared", "mcpx_solve_batch_shared_device", "mcpx_vjp_batch_shared",
            "mcpx_vjp_batch_shared_device", "mcpx_jvp_batch_shared", "mcpx_jvp_batch_shared_device",
            "mcpx_solve_vjp_batch_shared_device", "mcpx_vjp_batch_shared_reduce",
-           "mcpx_vjp_batch_shared_reduce_device")
+           "mcpx_vjp_batch_shared_reduce_device", "mcpx_jvp_batch_shared_dot", "mcpx_jvp_batch_shared_dot_device",
+           "mcpx_cond_batch_shared", "mcpx_cond_batch_shared_device")
 
 
 ABI_MAJOR = 2  # include/mcpx.h MCPX_VERSION / 10000
@@ -106,6 +107,10 @@ def lib():
     L.mcpx_vjp_batch_shared_reduce.argtypes = _abi.VJP_SHARED_REDUCE_ARGTYPES
     L.mcpx_vjp_batch_shared_reduce_device.restype = C.c_int
     L.mcpx_vjp_batch_shared_reduce_device.argtypes = _abi.VJP_SHARED_REDUCE_DEVICE_ARGTYPES
+    L.mcpx_jvp_batch_shared_dot.restype = C.c_int
+    L.mcpx_jvp_batch_shared_dot.argtypes = _abi.JVP_SHARED_DOT_ARGTYPES
+    L.mcpx_jvp_batch_shared_dot_device.restype = C.c_int
+    L.mcpx_jvp_batch_shared_dot_device.argtypes = _abi.JVP_SHARED_DOT_DEVICE_ARGTYPES
     I32P = C.POINTER(C.c_int32)
     L.mcpx_module_load.restype = C.c_int
     L.mcpx_module_load.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
@@ -136,6 +141,10 @@ def lib():
     L.mcpx_cond_batch_module.argtypes = [C.c_void_p, C.POINTER(_abi.Desc), P, P, P, P, C.c_int, P, P]
     L.mcpx_cond_batch_module_device.restype = C.c_int
     L.mcpx_cond_batch_module_device.argtypes = [C.c_void_p, C.POINTER(_abi.Desc), P, P, P, P, P, P, P]
+    L.mcpx_cond_batch_shared.restype = C.c_int
+    L.mcpx_cond_batch_shared.argtypes = L.mcpx_cond_batch.argtypes
+    L.mcpx_cond_batch_shared_device.restype = C.c_int
+    L.mcpx_cond_batch_shared_device.argtypes = L.mcpx_cond_batch_device.argtypes
     L.mcpx_host_register.restype = C.c_int
     L.mcpx_host_register.argtypes = [C.c_void_p, C.c_size_t]
     L.mcpx_host_unregister.restype = C.c_int

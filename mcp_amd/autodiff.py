@@ -11,6 +11,8 @@ mcpx_vjp_* / mcpx_jvp_*).
   rule of the traced family map (ThetaMap.vjp) on the host or device.
 * :func:`solve_dual` — the ForwardDiff.Dual method of `solve`
   (src/AutoDiff.jl:84-117): solution values plus partials ż = (∂z/∂θ) θ̇.
+* :func:`solve_shared_dual` — the same for a shared-matrix batch whose matrices move along
+  directions given once for the batch (mcpx_jvp_batch_shared_dot).
 * :func:`solve_torch` — the same pullback as a torch.autograd.Function, so a
   torch loss over (x, y, s) back-propagates into θ (the Zygote use of the
   reference's rrule, test/runtests.jl:65-85).
@@ -232,6 +234,46 @@ def solve_dual(solver_type, mcp, θ, θ_partials, *, num_devices: int = 0, **kwa
     return DualSolution(pick(sol.status), pick(sol.kkt_error), pick(sol.eps), pick(sol.x), pick(sol.y),
                         pick(sol.y),  # src/AutoDiff.jl:112: Dual(solution.y, s partials)
                         pick(xp), pick(yp), pick(sp_), s_value_true=pick(sol.s), sensitivity_status=pick(st))
+
+
+def solve_shared_dual(family: int, n: int, m: int, theta_shared, theta_var, shared_partials=None,
+                      var_partials=None, *, num_devices: int = 0, **solve_kwargs) -> DualSolution:
+    """Forward-mode twin of :func:`solve_shared_torch` for numpy inputs: the shared-matrix solve
+    (solve_batch_shared, `solve_kwargs`: its keyword arguments), then one tangent call at the
+    returned iterate.  theta_shared (shared_dim,), theta_var (B, n + m); shared_partials
+    (shared_dim, K): the partials of the shared block, the same for every instance (weights moved
+    along K directions); var_partials (B, n + m, K): those of the per-instance block — the layout
+    of :func:`solve_dual`.  At least one is required; a missing one is zero.  Returns a
+    DualSolution with (B, ·, K) partials (its `s` is the solution's y, as in solve_dual).
+    No (B, K, p) tangent is materialised: K·shared_dim + B·K·(n + m) doubles in its place."""
+    from . import _abi
+    from .batch import jvp_batch_shared, solve_batch_shared
+
+    if shared_partials is None and var_partials is None:
+        raise ValueError("solve_shared_dual needs shared_partials, var_partials or both")
+    tv = np.atleast_2d(np.asarray(theta_var, np.float64))
+    B, dv = tv.shape[0], _abi.theta_var_dim(family, n, m)
+    ds = _abi.theta_shared_dim(family, n, m)
+    sdot = vdot = None
+    if shared_partials is not None:
+        sp = np.asarray(shared_partials, np.float64)
+        if sp.ndim != 2 or sp.shape[0] != ds:
+            raise ValueError(f"shared_partials must be (shared_dim = {ds}, K)")
+        sdot = np.ascontiguousarray(sp.T)  # (K, shared_dim)
+    if var_partials is not None:
+        vp = np.asarray(var_partials, np.float64)
+        if vp.ndim != 3 or vp.shape[:2] != (B, dv):
+            raise ValueError(f"var_partials must be (B = {B}, n + m = {dv}, K)")
+        if sdot is not None and vp.shape[2] != sdot.shape[0]:
+            raise ValueError(f"shared_partials has {sdot.shape[0]} partials, var_partials {vp.shape[2]}")
+        vdot = np.ascontiguousarray(np.swapaxes(vp, 1, 2))  # (B, K, n + m)
+    sol = solve_batch_shared(family, n, m, theta_shared, tv, num_devices=num_devices, **solve_kwargs)
+    zd, st = jvp_batch_shared(family, n, m, theta_shared, sol["x"], sol["y"], sol["s"], vdot,
+                              num_devices=num_devices, shared_dot=sdot)  # (B, K, N)
+    zp = np.swapaxes(zd, 1, 2)  # (B, N, K)
+    return DualSolution(sol["status"], sol["kkt_error"], sol["eps"], sol["x"], sol["y"],
+                        sol["y"],  # src/AutoDiff.jl:112, as solve_dual
+                        zp[:, :n], zp[:, n:n + m], zp[:, n + m:], s_value_true=sol["s"], sensitivity_status=st)
 
 
 # ---------------------------------------------------------------------------

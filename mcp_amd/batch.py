@@ -489,22 +489,65 @@ def vjp_batch_shared(family: int, n: int, m: int, theta_shared, x, y, s, gx=None
     return dvar, st
 
 
-def jvp_batch_shared(family: int, n: int, m: int, theta_shared, x, y, s, var_dot, num_devices: int = 0) -> tuple:
+def _need_a_tangent(var_dot, shared_dot) -> None:
+    if var_dot is None and shared_dot is None:
+        raise ValueError("var_dot is None: give var_dot, shared_dot or both")
+
+
+def _shared_dot_partials(shared_dot_size: int, ds: int, vd_partials: int | None) -> int:
+    """K of a tangent call from shared_dot (K, shared_dim) and, when given, var_dot's K."""
+    if ds == 0 or shared_dot_size % ds:
+        raise ValueError(f"shared_dot must be (K, {ds}): K tangents of the shared block")
+    K = shared_dot_size // ds
+    if vd_partials is not None and vd_partials != K:
+        raise ValueError(f"shared_dot has {K} partials, var_dot {vd_partials}")
+    return K
+
+
+def jvp_batch_shared(family: int, n: int, m: int, theta_shared, x, y, s, var_dot, num_devices: int = 0,
+                     shared_dot=None) -> tuple:
     """jvp_batch for a shared-matrix batch (mcpx_jvp_batch_shared): var_dot (B, K, n + m), the
     tangents of the per-instance block (the matrix block's are zero) → (zdot (B, K, n+2m),
-    status (B,)), the bits of jvp_batch on θ̇ = [0 ‖ var_dot] for finite iterates."""
+    status (B,)), the bits of jvp_batch on θ̇ = [0 ‖ var_dot] for finite iterates.
+    `shared_dot` (K, shared_dim): the tangents of the shared block too, given once for the batch
+    (mcpx_jvp_batch_shared_dot) — the bits of jvp_batch on θ̇_{b,c} = [shared_dot_c ‖ var_dot_{b,c}],
+    whatever the iterate; var_dot may then be None (zero)."""
     theta_shared = _host_shared(family, n, m, theta_shared)
     B = _batch_of(np.atleast_2d(np.asarray(x)), np.atleast_2d(np.asarray(y)), n, m)
     dv = _abi.theta_var_dim(family, n, m)
-    vd = np.ascontiguousarray(var_dot, dtype=np.float64).reshape(B, -1, dv)
-    K = vd.shape[1]
+    _need_a_tangent(var_dot, shared_dot)
+    vd = None if var_dot is None else np.ascontiguousarray(var_dot, dtype=np.float64).reshape(B, -1, dv)
+    if shared_dot is None:
+        K = vd.shape[1]
+    else:
+        sd = np.ascontiguousarray(shared_dot, dtype=np.float64)
+        K = _shared_dot_partials(sd.size, theta_shared.size, None if vd is None else vd.shape[1])
     x, y, s = _host_f64(x, (B, n)), _host_f64(y, (B, m)), _host_f64(s, (B, m))
     zd = np.empty((B, K, n + 2 * m))
     st = np.empty(B, np.int32)
     desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(dv))
-    check(lib().mcpx_jvp_batch_shared(C.byref(desc), _ptr(theta_shared), _ptr(x), _ptr(y), _ptr(s), int(K), _ptr(vd),
-                                      int(num_devices), _ptr(zd), _ptr(st)))
+    if shared_dot is None:
+        check(lib().mcpx_jvp_batch_shared(C.byref(desc), _ptr(theta_shared), _ptr(x), _ptr(y), _ptr(s), int(K),
+                                          _ptr(vd), int(num_devices), _ptr(zd), _ptr(st)))
+    else:
+        check(lib().mcpx_jvp_batch_shared_dot(C.byref(desc), _ptr(theta_shared), _ptr(x), _ptr(y), _ptr(s), int(K),
+                                              _ptr(sd), _ptr(vd), int(num_devices), _ptr(zd), _ptr(st)))
     return zd, st
+
+
+def cond_batch_shared(family: int, n: int, m: int, theta_shared, x, y, s, num_devices: int = 0) -> tuple:
+    """cond_batch for a shared-matrix batch (mcpx_cond_batch_shared): theta_shared as in
+    solve_batch_shared, no per-instance θ (∇F_z does not contain it) → (rcond (B,), status (B,)),
+    the bits of cond_batch on the materialised θ′."""
+    theta_shared = _host_shared(family, n, m, theta_shared)
+    B = _batch_of(np.atleast_2d(np.asarray(x)), np.atleast_2d(np.asarray(y)), n, m)
+    x, y, s = _host_f64(x, (B, n)), _host_f64(y, (B, m)), _host_f64(s, (B, m))
+    rc = np.empty(B)
+    st = np.empty(B, np.int32)
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(_abi.theta_var_dim(family, n, m)))
+    check(lib().mcpx_cond_batch_shared(C.byref(desc), _ptr(theta_shared), _ptr(x), _ptr(y), _ptr(s),
+                                       int(num_devices), _ptr(rc), _ptr(st)))
+    return rc, st
 
 
 def vjp_batch_shared_device(family: int, n: int, m: int, theta_shared, x, y, s, gx=None, gy=None, gs=None,
@@ -530,16 +573,19 @@ def vjp_batch_shared_device(family: int, n: int, m: int, theta_shared, x, y, s, 
 
 
 def jvp_batch_shared_device(family: int, n: int, m: int, theta_shared, x, y, s, var_dot, zdot=None, status=None,
-                            stream=None):
+                            stream=None, shared_dot=None):
     """Device-tensor tangents of a shared-matrix batch: var_dot (B, K, n + m) →
-    (zdot (B, K, n+2m), status (B,))."""
+    (zdot (B, K, n+2m), status (B,)).  `shared_dot` (K, shared_dim), a device tensor: the tangents
+    of the shared block too (mcpx_jvp_batch_shared_dot_device); var_dot may then be None."""
     import torch
 
     sh = _dev_shared(family, n, m, theta_shared)
     B = _batch_of(x, y, n, m)
     dv = _abi.theta_var_dim(family, n, m)
-    vd = var_dot.reshape(B, -1, dv)
-    K = vd.shape[1]
+    _need_a_tangent(var_dot, shared_dot)
+    vd = None if var_dot is None else var_dot.reshape(B, -1, dv).contiguous()
+    K = vd.shape[1] if shared_dot is None else _shared_dot_partials(
+        shared_dot.numel(), theta_shared.numel(), None if vd is None else vd.shape[1])
     dev = theta_shared.device
     if zdot is None:
         zdot = torch.empty(B, K, n + 2 * m, dtype=torch.float64, device=dev)
@@ -547,10 +593,38 @@ def jvp_batch_shared_device(family: int, n: int, m: int, theta_shared, x, y, s, 
         status = torch.empty(B, dtype=torch.int32, device=dev)
     desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(dv))
     st = stream if stream is not None else torch.cuda.current_stream(dev)
-    check(lib().mcpx_jvp_batch_shared_device(C.byref(desc), sh, _dev_f64(x, "x"), _dev_f64(y, "y"), _dev_f64(s, "s"),
-                                             int(K), _dev_f64(vd.contiguous(), "var_dot"), _dev_f64(zdot, "zdot"),
-                                             status.data_ptr(), C.c_void_p(st.cuda_stream)))
+    if shared_dot is None:
+        check(lib().mcpx_jvp_batch_shared_device(C.byref(desc), sh, _dev_f64(x, "x"), _dev_f64(y, "y"),
+                                                 _dev_f64(s, "s"), int(K), _dev_f64(vd, "var_dot"),
+                                                 _dev_f64(zdot, "zdot"), status.data_ptr(),
+                                                 C.c_void_p(st.cuda_stream)))
+    else:
+        check(lib().mcpx_jvp_batch_shared_dot_device(C.byref(desc), sh, _dev_f64(x, "x"), _dev_f64(y, "y"),
+                                                     _dev_f64(s, "s"), int(K), _dev_f64(shared_dot, "shared_dot"),
+                                                     _dev_f64(vd, "var_dot"), _dev_f64(zdot, "zdot"),
+                                                     status.data_ptr(), C.c_void_p(st.cuda_stream)))
     return zdot, status
+
+
+def cond_batch_shared_device(family: int, n: int, m: int, theta_shared, x, y, s, rcond=None, status=None,
+                             stream=None):
+    """Device-tensor condition estimate of a shared-matrix batch (mcpx_cond_batch_shared_device),
+    enqueued on the current stream (no sync): (rcond (B,), status (B,) int32) tensors."""
+    import torch
+
+    sh = _dev_shared(family, n, m, theta_shared)
+    B = _batch_of(x, y, n, m)
+    dev = theta_shared.device
+    if rcond is None:
+        rcond = torch.empty(B, dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(_abi.theta_var_dim(family, n, m)))
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    check(lib().mcpx_cond_batch_shared_device(C.byref(desc), sh, _dev_f64(x, "x"), _dev_f64(y, "y"), _dev_f64(s, "s"),
+                                              _dev_f64(rcond, "rcond"), status.data_ptr(),
+                                              C.c_void_p(st.cuda_stream)))
+    return rcond, status
 
 
 def solve_vjp_batch_shared_device(family: int, n: int, m: int, theta_shared, theta_var, out: dict | None = None, *,

@@ -84,5 +84,8 @@ hipError_t launch_sens_wg(int family, bool jvp, int nv, const wg::WgSensArgs& a,
 // The same on a shared-matrix batch (sens_inst_wg_shared.hip; sens_wg_impl.hpp SPLIT).
 const void* sens_wg_shared_kernel(int family, bool jvp, int nv);
 hipError_t launch_sens_wg_shared(int family, bool jvp, int nv, const wg::WgSensArgs& a, int grid, hipStream_t st);
+// The JVP of mcpx_jvp_batch_shared_dot* (sens_inst_wg_shared_dot.hip; SPLIT = kThetaSplitDot).
+const void* sens_wg_shared_dot_kernel(int family, int nv);
+hipError_t launch_sens_wg_shared_dot(int family, int nv, const wg::WgSensArgs& a, int grid, hipStream_t st);
 
 }  // namespace mcpx

@@ -695,12 +695,15 @@ enum SensKind { kVjp, kJvp, kCond };
 // (larger QP / affine systems in the dimension bucket `nv`, and every generated module).
 // `split`: a shared-matrix batch (mcpx_vjp_batch_shared*, mcpx_jvp_batch_shared*) — the SPLIT
 // kernels, which read one matrix block and write / read the per-instance block's n + m doubles.
+// `dot` (with split, a JVP: mcpx_jvp_batch_shared_dot*): the kThetaSplitDot kernels, which take the
+// matrix block's tangents from SensArgs::shared_dot.
 struct SensPlan {
   int nmax = 0;
   bool wg = false;
   int nv = 0;
   mcpx_module* mod = nullptr;
   bool split = false;
+  bool dot = false;
 };
 
 // Validates a sensitivity call; fills the scalar part of the args (the caller's pointers,
@@ -708,7 +711,7 @@ struct SensPlan {
 // is checked as in the shared solve, a->p is the per-instance dimension n + m (the stride of the
 // outputs and tangents), and the kernels read a->theta for every instance.
 int prepare_sens(const mcpx_desc* d, mcpx::SensArgs* a, SensPlan* plan, SensKind kind, mcpx_module* mod,
-                 bool split = false) {
+                 bool split = false, bool dot = false) {
   if (!d) return fail(MCPX_EINVAL, "desc must be non-NULL");
   int64_t pd;
   if (const int rc = check_desc(d, mod, &pd, kSensWords, split)) return rc;
@@ -717,6 +720,7 @@ int prepare_sens(const mcpx_desc* d, mcpx::SensArgs* a, SensPlan* plan, SensKind
   *plan = SensPlan{};
   plan->mod = mod;
   plan->split = split;
+  plan->dot = split && dot && kind == kJvp;
   if (mod) {
     if (!mod->has(jvp ? MCPX_MODULE_JVP : MCPX_MODULE_VJP))
       return fail(MCPX_EUNSUPPORTED, "the generated module has no %s kernel (n=%d m=%d: not even a 4-column LU panel of "
@@ -742,13 +746,15 @@ int prepare_sens(const mcpx_desc* d, mcpx::SensArgs* a, SensPlan* plan, SensKind
 }
 
 // The argument checks after prepare_sens; an empty batch reads nothing and passes.
-int sens_inputs_ok(const mcpx_desc* d, const mcpx::SensArgs& a) {
+// `dot` (mcpx_jvp_batch_shared_dot*): shared_dot is the required tangent, theta_dot (var_dot) may be NULL.
+int sens_inputs_ok(const mcpx_desc* d, const mcpx::SensArgs& a, bool dot = false) {
   if (a.n_partials < 0) return fail(MCPX_EINVAL, "negative n_partials");
   if (d->batch == 0) return MCPX_OK;
   if (!a.theta || !a.out) return fail(MCPX_EINVAL, "theta and the output array must be non-NULL");
   if ((d->n > 0 && !a.x) || (d->m > 0 && (!a.y || !a.s)))
     return fail(MCPX_EINVAL, "solution arrays x/y/s must be non-NULL");
-  if (a.n_partials > 0 && !a.theta_dot) return fail(MCPX_EINVAL, "theta_dot is NULL");
+  if (a.n_partials > 0 && dot && !a.shared_dot) return fail(MCPX_EINVAL, "shared_dot is NULL");
+  if (a.n_partials > 0 && !dot && !a.theta_dot) return fail(MCPX_EINVAL, "theta_dot is NULL");
   return MCPX_OK;
 }
 
@@ -783,8 +789,9 @@ int launch_sens_wg_impl(bool jvp, const mcpx_desc* d, const mcpx::SensArgs& a, c
     const int rc = module_function(plan.mod, name, name, &k.f, &dev);
     if (rc) return rc;
   } else {
-    k.sym = plan.split ? mcpx::sens_wg_shared_kernel(a.family, jvp, plan.nv)
-                       : mcpx::sens_wg_kernel(a.family, jvp, plan.nv);
+    k.sym = plan.dot     ? mcpx::sens_wg_shared_dot_kernel(a.family, plan.nv)
+            : plan.split ? mcpx::sens_wg_shared_kernel(a.family, jvp, plan.nv)
+                         : mcpx::sens_wg_kernel(a.family, jvp, plan.nv);
     if (!k.sym) return fail(MCPX_EUNSUPPORTED, "no workgroup sensitivity kernel for family %d, dim %d", a.family, plan.nv);
   }
   wg::WgSensArgs w = wg::sens_layout(jvp, a.mode, a.n, a.m, a.p, a.n_partials,
@@ -792,6 +799,7 @@ int launch_sens_wg_impl(bool jvp, const mcpx_desc* d, const mcpx::SensArgs& a, c
   return launch_persistent(k, -1, d->batch, w, wg::kSensWorkCap, st, "workgroup sensitivity", [&](int64_t b0, int grid) {
     w.s = sens_chunk(a, jvp, b0);
     if (plan.mod) return launch_module(k.f, grid, k.threads, &w, st);
+    if (plan.dot) return mcpx::launch_sens_wg_shared_dot(a.family, plan.nv, w, grid, st);
     return plan.split ? mcpx::launch_sens_wg_shared(a.family, jvp, plan.nv, w, grid, st)
                       : mcpx::launch_sens_wg(a.family, jvp, plan.nv, w, grid, st);
   });
@@ -805,7 +813,9 @@ int launch_sens(bool jvp, const mcpx_desc* d, const mcpx::SensArgs& a, const Sen
     const int64_t nb = std::min(wg::kChunk, d->batch - b0);
     const mcpx::SensArgs c = sens_chunk(a, jvp, b0);
     // the VJP factors the slack-eliminated (n+m)-dim system, the JVP the full n+2m
-    if (plan.split)
+    if (plan.dot)
+      HIP_TRY(mcpx::launch_jvp_shared_dot(plan.nmax, c, nb, st));
+    else if (plan.split)
       HIP_TRY(jvp ? mcpx::launch_jvp_shared(plan.nmax, c, nb, st)
                   : mcpx::launch_vjp_shared(pick_nmax(a.n + a.m), c, nb, st));
     else
@@ -816,14 +826,15 @@ int launch_sens(bool jvp, const mcpx_desc* d, const mcpx::SensArgs& a, const Sen
 
 // One device's share [b0, b0+nb) of a host-buffer sensitivity call (`a`: host pointers).
 // A shared-matrix call (plan.split) uploads its one matrix block, no per-instance θ, and brings
-// back a.p = n + m doubles per instance.
+// back a.p = n + m doubles per instance (the VJP; rcond: one double).  plan.dot: the one
+// [K × shared_dim] block of matrix tangents goes up once as well.
 int sens_shard(bool jvp, int dev, const mcpx_desc* d, const mcpx::SensArgs& a, const SensPlan& plan, int64_t b0,
                int64_t nb) {
   HIP_TRY(hipSetDevice(dev));
   int rc = check_device(dev);
   if (rc) return rc;
   const int n = d->n, m = d->m;
-  DevBuf<double> th, dx, dy, ds, dgx, dgy, dgs, dtd, dout;
+  DevBuf<double> th, dx, dy, ds, dgx, dgy, dgs, dtd, dsd, dout;
   DevBuf<int32_t> dst;
   auto up = [&](DevBuf<double>& b, const double* h, size_t per) -> hipError_t {
     if (!h || !per || !nb) return hipSuccess;
@@ -834,6 +845,11 @@ int sens_shard(bool jvp, int dev, const mcpx_desc* d, const mcpx::SensArgs& a, c
     const int64_t ds = mcpx_theta_shared_dim(d->family, n, m);
     HIP_TRY(th.alloc((size_t)std::max<int64_t>(ds, 1)));
     if (ds > 0) HIP_TRY(hipMemcpy(th.p, a.theta, sizeof(double) * (size_t)ds, hipMemcpyHostToDevice));
+    const size_t nsd = plan.dot ? (size_t)a.n_partials * (size_t)ds : 0;
+    if (nsd) {
+      HIP_TRY(dsd.alloc(nsd));
+      HIP_TRY(hipMemcpy(dsd.p, a.shared_dot, sizeof(double) * nsd, hipMemcpyHostToDevice));
+    }
   } else {
     HIP_TRY(up(th, a.theta, (size_t)d->theta_ld));
   }
@@ -855,6 +871,7 @@ int sens_shard(bool jvp, int dev, const mcpx_desc* d, const mcpx::SensArgs& a, c
   da.gy = dgy.p;
   da.gs = dgs.p;
   da.theta_dot = dtd.p;
+  da.shared_dot = dsd.p ? dsd.p : th.p;  // (an empty matrix block, n = 0: never read)
   // an empty output (p = 0, or K = 0) still needs a valid base pointer
   da.out = dout.p ? dout.p : (double*)th.p;
   da.status = dst.p;
@@ -871,11 +888,11 @@ int sens_shard(bool jvp, int dev, const mcpx_desc* d, const mcpx::SensArgs& a, c
 // The device-buffer sensitivity entries (`a`: the caller's pointers, n_partials): enqueued
 // on `stream` of the current device.  `split`: a.theta is the matrix block of a shared-matrix batch.
 int sens_device(SensKind kind, mcpx_module* mod, const mcpx_desc* d, mcpx::SensArgs a, void* stream,
-                bool split = false) {
+                bool split = false, bool dot = false) {
   SensPlan plan;
   int rc;
-  if ((rc = prepare_sens(d, &a, &plan, kind, mod, split))) return rc;
-  if ((rc = sens_inputs_ok(d, a)) || d->batch == 0) return rc;
+  if ((rc = prepare_sens(d, &a, &plan, kind, mod, split, dot))) return rc;
+  if ((rc = sens_inputs_ok(d, a, dot)) || d->batch == 0) return rc;
   int dev = 0;
   if ((rc = current_device(&dev))) return rc;
   // empty x/y blocks (n = 0 or m = 0) still need a valid base pointer
@@ -887,11 +904,11 @@ int sens_device(SensKind kind, mcpx_module* mod, const mcpx_desc* d, mcpx::SensA
 
 // The host-buffer sensitivity entries: contiguous shards over the devices.
 int sens_host(SensKind kind, mcpx_module* mod, const mcpx_desc* d, mcpx::SensArgs a, int num_devices,
-              bool split = false) {
+              bool split = false, bool dot = false) {
   SensPlan plan;
   int rc;
-  if ((rc = prepare_sens(d, &a, &plan, kind, mod, split))) return rc;
-  if ((rc = sens_inputs_ok(d, a)) || d->batch == 0) return rc;
+  if ((rc = prepare_sens(d, &a, &plan, kind, mod, split, dot))) return rc;
+  if ((rc = sens_inputs_ok(d, a, dot)) || d->batch == 0) return rc;
   return run_shards(num_devices, d->batch, [&](int dev, int64_t b0, int64_t nb) {
     return sens_shard(kind != kVjp, dev, d, a, plan, b0, nb);
   });
@@ -1405,6 +1422,36 @@ int mcpx_jvp_batch_shared(const mcpx_desc* d, const double* theta_shared, const 
   a.n_partials = n_partials;
   a.theta_dot = var_dot;
   return sens_host(kJvp, nullptr, d, a, num_devices, true);
+}
+
+int mcpx_jvp_batch_shared_dot_device(const mcpx_desc* d, const double* theta_shared, const double* x,
+                                     const double* y, const double* s, int32_t n_partials, const double* shared_dot,
+                                     const double* var_dot, double* zdot, int32_t* status, void* stream) {
+  mcpx::SensArgs a = sens_args(theta_shared, x, y, s, zdot, status);
+  a.n_partials = n_partials;
+  a.shared_dot = shared_dot;
+  a.theta_dot = var_dot;
+  return sens_device(kJvp, nullptr, d, a, stream, true, true);
+}
+
+int mcpx_jvp_batch_shared_dot(const mcpx_desc* d, const double* theta_shared, const double* x, const double* y,
+                              const double* s, int32_t n_partials, const double* shared_dot, const double* var_dot,
+                              int num_devices, double* zdot, int32_t* status) {
+  mcpx::SensArgs a = sens_args(theta_shared, x, y, s, zdot, status);
+  a.n_partials = n_partials;
+  a.shared_dot = shared_dot;
+  a.theta_dot = var_dot;
+  return sens_host(kJvp, nullptr, d, a, num_devices, true, true);
+}
+
+int mcpx_cond_batch_shared(const mcpx_desc* d, const double* theta_shared, const double* x, const double* y,
+                           const double* s, int num_devices, double* rcond, int32_t* status) {
+  return sens_host(kCond, nullptr, d, sens_args(theta_shared, x, y, s, rcond, status), num_devices, true);
+}
+
+int mcpx_cond_batch_shared_device(const mcpx_desc* d, const double* theta_shared, const double* x, const double* y,
+                                  const double* s, double* rcond, int32_t* status, void* stream) {
+  return sens_device(kCond, nullptr, d, sens_args(theta_shared, x, y, s, rcond, status), stream, true);
 }
 
 int mcpx_host_register(void* ptr, size_t bytes) {

@@ -1,4 +1,4 @@
-// jvp_kernel instantiations with the SPLIT flag (sens_kernel_impl.hpp) for
+// jvp_kernel instantiations with SPLIT = kThetaSplit (sens_kernel_impl.hpp) for
 // NMAX ∈ {8,16,24,32,48,64} ≥ n + 2m, QP and affine families: the tangents of a
 // shared-matrix batch (mcpx_jvp_batch_shared*) — rows of ∇F_z from the one matrix block,
 // right-hand sides from the per-instance block's tangents.
@@ -10,9 +10,9 @@ namespace {
 template <int NMAX>
 hipError_t go_jvp_shared(const SensArgs& a, int64_t batch, hipStream_t st) {
   if (a.family == MCPX_FAMILY_QP)
-    hipLaunchKernelGGL((jvp_kernel<NMAX, 0, true>), dim3((unsigned)batch), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((jvp_kernel<NMAX, 0, kThetaSplit>), dim3((unsigned)batch), dim3(64), 0, st, a);
   else
-    hipLaunchKernelGGL((jvp_kernel<NMAX, 1, true>), dim3((unsigned)batch), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((jvp_kernel<NMAX, 1, kThetaSplit>), dim3((unsigned)batch), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 }  // namespace

@@ -8,7 +8,7 @@ namespace mcpx {
 
 template <int FAMILY, bool JVP, int NV>
 __global__ __launch_bounds__(wg::kThreads) void sens_wg_shared_kernel_t(const wg::WgSensArgs args) {
-  wg::sens_instances<FAMILY, JVP, NV, NV, wg::NoGen, wg::kNB, true>(args);
+  wg::sens_instances<FAMILY, JVP, NV, NV, wg::NoGen, wg::kNB, kThetaSplit>(args);
 }
 
 namespace {

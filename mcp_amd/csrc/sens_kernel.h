@@ -33,7 +33,18 @@ struct SensArgs {
   // l = Σ ½ a z² + b·z (e.g. a = 2, b = 0: f = Σx² + Σy², test/runtests.jl:72-75),
   // computed in the kernel as a·z + b (two roundings, no fma)
   double ga_x, ga_y, ga_s;
+  // mcpx_jvp_batch_shared_dot*: the tangents of the shared matrix block, [K × shared_dim], the
+  // same for every instance (theta_dot is then the per-instance block's, or NULL = +0.0).
+  // Last, so that the kernels of generated modules built against this header are unaffected.
+  const double* shared_dot;
 };
+
+// Where a kernel's θ (and a JVP's θ̇) comes from.  kThetaFull: instance b's θ′ at
+// theta + b·theta_ld, θ̇ [B × K × p].  kThetaSplit (a shared-matrix batch): theta is the ONE
+// matrix block; the JVP takes the per-instance block's tangents only (the matrix block's are
+// zero).  kThetaSplitDot (mcpx_jvp_batch_shared_dot*): as kThetaSplit, with the matrix block's
+// tangents in shared_dot.
+constexpr int kThetaFull = 0, kThetaSplit = 1, kThetaSplitDot = 2;
 
 // One cotangent entry g = a·z + b (a = 0 → b, 0 when b is absent; b absent → a·z).
 __device__ __forceinline__ double affine_ct(double a, double z, const double* b) {
@@ -62,6 +73,9 @@ hipError_t launch_jvp(int nmax, const SensArgs& a, int64_t batch, hipStream_t st
 // gradient of the per-instance block / a.theta_dot its [B × K × (n+m)] tangents.
 hipError_t launch_vjp_shared(int nmax, const SensArgs& a, int64_t batch, hipStream_t st);
 hipError_t launch_jvp_shared(int nmax, const SensArgs& a, int64_t batch, hipStream_t st);
+// The tangents of a shared-matrix batch along a direction of the shared block too
+// (mcpx_jvp_batch_shared_dot*): a.shared_dot [K × shared_dim], a.theta_dot [B × K × (n+m)] or NULL.
+hipError_t launch_jvp_shared_dot(int nmax, const SensArgs& a, int64_t batch, hipStream_t st);
 
 // The reduced gradient of the shared block (mcpx_vjp_batch_shared_reduce*, shared_reduce.hip).
 struct ReduceArgs {

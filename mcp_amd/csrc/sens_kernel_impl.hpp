@@ -111,28 +111,49 @@ __device__ __forceinline__ void assemble_pattern_row(const double* __restrict__ 
   }
 }
 
-// (∇F_θ θ̇)_ln for the row pattern of ∇F_z (TR = false) applied to the tangent
-// θ̇: the x-block chain, then the y-block chain, then the θ-only term
-// (QP: −ϕ̇_i / −ḃ_q, affine: +ġ_i / +ḣ_q); complementarity rows: 0.
-// fma_chain order of oracle dtheta_row().
-template <int FAMILY>
-__device__ __forceinline__ double dtheta_row(const double* __restrict__ d, const RowPattern& P, const double* zs,
-                                             int ln, int n, int m) {
-  const int64_t nn = (int64_t)n * n, nm = (int64_t)n * m, mm = (int64_t)m * m;
+// The two fma chains of (∇F_θ θ̇)_ln: the row pattern of ∇F_z (TR = false) applied to the
+// tangent `dm` of the matrix block (the RowPattern offsets count from it), the x-block chain,
+// then the y-block chain.  fma_chain order of oracle dtheta_row().
+__device__ __forceinline__ double dtheta_chains(const double* __restrict__ dm, const RowPattern& P, const double* zs,
+                                                int n, int m) {
   double acc = 0.0;
   if (P.usex)
     for (int j = 0; j < n; ++j) {
-      const double t = d[P.ox + (int64_t)j * P.sx];
+      const double t = dm[P.ox + (int64_t)j * P.sx];
       acc = fma(P.negx ? -t : t, zs[j], acc);
     }
   if (P.usey)
     for (int k = 0; k < m; ++k) {
-      const double t = d[P.oy + (int64_t)k * P.sy];
+      const double t = dm[P.oy + (int64_t)k * P.sy];
       acc = fma(P.negy ? -t : t, zs[n + k], acc);
     }
+  return acc;
+}
+
+// (∇F_θ θ̇)_ln on one dense θ̇ (mcpx_jvp_batch*): the chains, then the θ-only term
+// (QP: −ϕ̇_i / −ḃ_q, affine: +ġ_i / +ḣ_q); complementarity rows: 0.
+template <int FAMILY>
+__device__ __forceinline__ double dtheta_row(const double* __restrict__ d, const RowPattern& P, const double* zs,
+                                             int ln, int n, int m) {
+  const int64_t nn = (int64_t)n * n, nm = (int64_t)n * m, mm = (int64_t)m * m;
+  const double acc = dtheta_chains(d, P, zs, n, m);
   if (ln < n) return FAMILY == 0 ? acc - d[nn + nm + m + ln] : acc + d[nn + 2 * nm + mm + ln];
   if (ln < n + m) return FAMILY == 0 ? acc - d[nn + nm + (ln - n)] : acc + d[nn + 2 * nm + mm + n + (ln - n)];
   return 0.0;
+}
+
+// The same with the two blocks of θ̇ apart (mcpx_jvp_batch_shared_dot*): the chains on the
+// batch's one matrix tangent `dm`, the θ-only term from the instance's [ḃ; ϕ̇] / [ġ; ḣ] in `dv`,
+// or from +0.0 when dv is NULL — the step still runs (acc + (+0.0) is not acc for acc = −0.0).
+template <int FAMILY>
+__device__ __forceinline__ double dtheta_row_split(const double* __restrict__ dm, const double* __restrict__ dv,
+                                                   const RowPattern& P, const double* zs, int ln, int n, int m) {
+  const double acc = dtheta_chains(dm, P, zs, n, m);
+  if (ln >= n + m) return 0.0;
+  // QP: ϕ̇_i at m + i, ḃ_q at q; affine: ġ_i at i, ḣ_q at n + q
+  const int iv = FAMILY == 0 ? (ln < n ? m + ln : ln - n) : ln;
+  const double t = dv ? dv[iv] : 0.0;
+  return FAMILY == 0 ? acc - t : acc + t;
 }
 
 // a[j] ← fma(−l, u_j, a[j]) for j in (k, NMAX) and r[c] ← fma(−l, u_{NMAX+c}, r[c])
@@ -499,9 +520,11 @@ __device__ __forceinline__ bool fused_vjp(const KernelArgs& A, int64_t inst, int
   return done;
 }
 
-// SPLIT: A.theta is the one matrix block of a shared-matrix batch, A.theta_dot is
-// [B × K × (n+m)] (the per-instance block's tangents; the matrix block's are zero).
-template <int NMAX, int FAMILY, bool SPLIT = false>
+// SPLIT (sens_kernel.h): kThetaSplit — A.theta is the one matrix block of a shared-matrix batch,
+// A.theta_dot is [B × K × (n+m)] (the per-instance block's tangents; the matrix block's are
+// zero).  kThetaSplitDot — the matrix block's tangents are A.shared_dot [K × shared_dim], the
+// same rows for every instance (they stay in L2), and A.theta_dot may be NULL.
+template <int NMAX, int FAMILY, int SPLIT = kThetaFull>
 __global__ __launch_bounds__(64) void jvp_kernel(const SensArgs A) {
   constexpr int R = MCPX_JVP_RHS;
   __shared__ double zs[64];
@@ -509,7 +532,7 @@ __global__ __launch_bounds__(64) void jvp_kernel(const SensArgs A) {
   const int64_t inst = blockIdx.x;
   const int n = A.n, m = A.m, N = n + 2 * m, K = A.n_partials;
   const double* th_;
-  if constexpr (SPLIT) th_ = A.theta;
+  if constexpr (SPLIT != kThetaFull) th_ = A.theta;
   else th_ = A.theta + inst * A.theta_ld;
   const double* th = th_;
   load_z(A, inst, ln, zs);
@@ -523,7 +546,11 @@ __global__ __launch_bounds__(64) void jvp_kernel(const SensArgs A) {
     for (int c = 0; c < R; ++c) {
       r[c] = 0.0;
       if (c0 + c < K) {
-        if constexpr (SPLIT) {
+        if constexpr (SPLIT == kThetaSplitDot) {
+          const int64_t ds = (int64_t)n * n + (FAMILY == 0 ? (int64_t)n * m : 2 * (int64_t)n * m + (int64_t)m * m);
+          const double* dv = A.theta_dot ? A.theta_dot + (inst * K + c0 + c) * (n + m) : nullptr;
+          r[c] = -dtheta_row_split<FAMILY>(A.shared_dot + (c0 + c) * ds, dv, P, zs, ln, n, m);
+        } else if constexpr (SPLIT == kThetaSplit) {
           r[c] = -dvar_row<FAMILY>(A.theta_dot + (inst * K + c0 + c) * (n + m), ln, n, m);
         } else {
           const double* d = A.theta_dot + (inst * K + c0 + c) * A.p;

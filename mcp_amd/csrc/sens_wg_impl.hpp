@@ -25,34 +25,49 @@ namespace mcpx {
 namespace wg {
 
 // (∇F_θ θ̇)_i of the QP / affine families (oracle dtheta_row): the θ-pattern of row i
-// applied to the tangent d, fma chains over x then y, then the θ-only term.
-template <int FAMILY>
-__device__ __forceinline__ double dtheta_row_aff(const double* __restrict__ d, const double* zs, int n, int m,
-                                                 int i) {
-  const int64_t nn = (int64_t)n * n, nm = (int64_t)n * m, mm = (int64_t)m * m;
+// applied to the tangent, fma chains over x then y, then the θ-only term.  dm: the tangent of
+// the matrix block; dv: the tangent of the per-instance block, [ḃ; ϕ̇] / [ġ; ḣ].  VNULL
+// (mcpx_jvp_batch_shared_dot* without a var_dot): dv may be NULL = +0.0; the last step still runs.
+template <int FAMILY, bool VNULL>
+__device__ __forceinline__ double dtheta_row_aff_split(const double* __restrict__ dm, const double* __restrict__ dv,
+                                                       const double* zs, int n, int m, int i) {
+  const int64_t nn = (int64_t)n * n, nm = (int64_t)n * m;
+  auto var = [&](int t) {
+    if constexpr (VNULL) return dv ? dv[t] : 0.0;
+    else return dv[t];
+  };
   double acc = 0.0;
   if (i < n) {
-    for (int j = 0; j < n; ++j) acc = fma(d[(int64_t)j * n + i], zs[j], acc);
+    for (int j = 0; j < n; ++j) acc = fma(dm[(int64_t)j * n + i], zs[j], acc);
     if constexpr (FAMILY == MCPX_FAMILY_QP) {
-      for (int k = 0; k < m; ++k) acc = fma(-d[nn + (int64_t)i * m + k], zs[n + k], acc);
-      return acc - d[nn + nm + m + i];
+      for (int k = 0; k < m; ++k) acc = fma(-dm[nn + (int64_t)i * m + k], zs[n + k], acc);
+      return acc - var(m + i);
     } else {
-      for (int k = 0; k < m; ++k) acc = fma(d[nn + (int64_t)k * n + i], zs[n + k], acc);
-      return acc + d[nn + 2 * nm + mm + i];
+      for (int k = 0; k < m; ++k) acc = fma(dm[nn + (int64_t)k * n + i], zs[n + k], acc);
+      return acc + var(i);
     }
   }
   if (i < n + m) {
     const int k = i - n;
     if constexpr (FAMILY == MCPX_FAMILY_QP) {
-      for (int j = 0; j < n; ++j) acc = fma(d[nn + (int64_t)j * m + k], zs[j], acc);
-      return acc - d[nn + nm + k];
+      for (int j = 0; j < n; ++j) acc = fma(dm[nn + (int64_t)j * m + k], zs[j], acc);
+      return acc - var(k);
     } else {
-      for (int j = 0; j < n; ++j) acc = fma(d[nn + nm + (int64_t)j * m + k], zs[j], acc);
-      for (int q = 0; q < m; ++q) acc = fma(d[nn + 2 * nm + (int64_t)q * m + k], zs[n + q], acc);
-      return acc + d[nn + 2 * nm + mm + n + k];
+      for (int j = 0; j < n; ++j) acc = fma(dm[nn + nm + (int64_t)j * m + k], zs[j], acc);
+      for (int q = 0; q < m; ++q) acc = fma(dm[nn + 2 * nm + (int64_t)q * m + k], zs[n + q], acc);
+      return acc + var(n + k);
     }
   }
   return 0.0;
+}
+
+// The same on one dense θ̇ (mcpx_jvp_batch*): the per-instance block follows the matrix block.
+template <int FAMILY>
+__device__ __forceinline__ double dtheta_row_aff(const double* __restrict__ d, const double* zs, int n, int m,
+                                                 int i) {
+  const int64_t nn = (int64_t)n * n, nm = (int64_t)n * m, mm = (int64_t)m * m;
+  return dtheta_row_aff_split<FAMILY, false>(d, d + (FAMILY == MCPX_FAMILY_QP ? nn + nm : nn + 2 * nm + mm), zs, n,
+                                             m, i);
 }
 
 // (∇F_θ θ̇)_i of a generated module (oracle dtheta_row_nl): the θ columns of row i ascending.
@@ -261,11 +276,14 @@ __device__ __forceinline__ double cond_one(double* __restrict__ A, int ld, int N
 // does not fit the LDS pass 8 or 4 (csrc/ipm_nl_kernel.hpp, MCPX_NL_SENS_NB_*).
 // SPLIT (QP / affine, a shared-matrix batch: mcpx_vjp_batch_shared*, mcpx_jvp_batch_shared*):
 // a.theta is the ONE matrix block of every instance and a.p = n + m, the stride of the outputs
-// [∂b; ∂ϕ] / [∂g; ∂h] and of the tangents of the per-instance block.
-template <int FAMILY, bool JVP, int NVMAX, int NSMAX, class GEN, int NB = kNB, bool SPLIT = false>
+// [∂b; ∂ϕ] / [∂g; ∂h] and of the tangents of the per-instance block.  SPLIT = kThetaSplitDot
+// (mcpx_jvp_batch_shared_dot*, JVP only): the matrix block's tangents come from a.shared_dot
+// [K × shared_dim], the same for every instance, and a.theta_dot may be NULL.
+template <int FAMILY, bool JVP, int NVMAX, int NSMAX, class GEN, int NB = kNB, int SPLIT = kThetaFull>
 __device__ __forceinline__ void sens_instances(const WgSensArgs& W) {
   constexpr bool NL = FAMILY == MCPX_FAMILY_NONLINEAR;
   static_assert(!SPLIT || !NL, "generated modules have no split θ");
+  static_assert(SPLIT != kThetaSplitDot || JVP, "shared_dot is a tangent");
   __shared__ SolveShared<NVMAX, NSMAX, false, false, NB> S;  // several right-hand sides: the HBM LU
   const SensArgs& a = W.s;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -339,9 +357,17 @@ __device__ __forceinline__ void sens_instances(const WgSensArgs& W) {
             if (j < ns) {
               v = jac<FAMILY, GEN>(th, blk, zs, n, m, r, j);
             } else {
-              const double* d = a.theta_dot + (inst * K + c0 + (j - ns)) * p;
-              if constexpr (SPLIT) v = -dvar_row<FAMILY>(d, r, n, m);
-              else v = -(NL ? dtheta_row_nl<GEN>(dth, d, nr, r) : dtheta_row_aff<FAMILY>(d, zs, n, m, r));
+              if constexpr (SPLIT == kThetaSplitDot) {
+                const int64_t ds = (int64_t)n * n + (FAMILY == MCPX_FAMILY_QP ? (int64_t)n * m
+                                                                              : 2 * (int64_t)n * m + (int64_t)m * m);
+                const int c = c0 + (j - ns);
+                const double* dv = a.theta_dot ? a.theta_dot + (inst * K + c) * p : nullptr;
+                v = -dtheta_row_aff_split<FAMILY, true>(a.shared_dot + c * ds, dv, zs, n, m, r);
+              } else {
+                const double* d = a.theta_dot + (inst * K + c0 + (j - ns)) * p;
+                if constexpr (SPLIT) v = -dvar_row<FAMILY>(d, r, n, m);
+                else v = -(NL ? dtheta_row_nl<GEN>(dth, d, nr, r) : dtheta_row_aff<FAMILY>(d, zs, n, m, r));
+              }
             }
           } else {
             if (j < n) {
