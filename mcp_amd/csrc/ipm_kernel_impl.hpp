@@ -509,10 +509,8 @@ __device__ __forceinline__ double dot_strided(const double* __restrict__ p, int 
 // element (≈ 96 VALU a Newton step at C3), here one add (MCPX_RES_INC; same loads, same
 // bits; C3 8,192: 12.56 against 12.21 M solves/s, profiles/r05/ab_res_inc.jsonl).
 template <int BATCH>
-__device__ __forceinline__ double dot_strided_inc(const double* __restrict__ p, int st, const double* q, int cnt,
-                                                  double acc) {
-  const int64_t sb = (int64_t)st * 8;
-  const char* pc = (const char*)p;
+__device__ __forceinline__ double dot_strided_inc_b(const char* pc, uint64_t sb, const double* q, int cnt,
+                                                    double acc) {  // byte pointer, byte stride
   for (int j0 = 0; j0 < cnt; j0 += BATCH) {
     double t[BATCH];
 #pragma unroll
@@ -528,6 +526,11 @@ __device__ __forceinline__ double dot_strided_inc(const double* __restrict__ p, 
   }
   return acc;
 }
+template <int BATCH>
+__device__ __forceinline__ double dot_strided_inc(const double* __restrict__ p, int st, const double* q, int cnt,
+                                                  double acc) {
+  return dot_strided_inc_b<BATCH>((const char*)p, (uint64_t)((int64_t)st * 8), q, cnt, acc);
+}
 
 // SCHUR path (QP family, and the affine family with ∂H/∂y ≡ 0), part 1: residuals.
 // x-lanes compute F_G, y-lanes (which also own s_k) F_H and F_C; same fma order as
@@ -536,16 +539,43 @@ __device__ __forceinline__ double dot_strided_inc(const double* __restrict__ p, 
 // negated in the same layout (QP: A again, since ∂G/∂y = −Aᵀ; affine: −Qᵀ); `tb` the
 // constants b then ϕ (affine: −h then −g, so that acc − b = acc + h bit for bit).
 // QP: θ itself (lda = m) or the wave's LDS copy, tq = ta, tb = ta + n·lda.
-template <int BATCH>
+// MCPX_RES_HOIST (compile-time n = NS, M in θ and the A block in the wave's LDS copy): the
+// lane's pointer and byte stride of the residual's M·x | A·x stream are fixed for an instance
+// (res_stream() below); the kernel forms them once, ahead of the Newton loops, and hands them in
+// as `rp` / `rsb` (3 VGPRs for the whole solve) instead of rebuilding them, LDS aperture and
+// x-lane / y-lane / idle selects included, at every step.
+#ifndef MCPX_RES_HOIST
+#define MCPX_RES_HOIST 1
+#endif
+// Lanes < NS read column `lane` of M (stride NS); every other lane a row of the LDS copy `ta`
+// (leading dimension LS): rows 0 .. m − 1 are A's, the idle lanes' rows up to 63 − NS still lie
+// inside the copy (NS·LS + m + NS doubles; their sums are never used), where the general form
+// parks them on θ[0] with stride 0 at the price of a second select.  Same loads in the lanes
+// that count, same bits.
+template <int NS, int LS>
+__device__ __forceinline__ void res_stream(const double* th, const double* ta, int lane, const char*& rp,
+                                           uint32_t& rsb) {
+  static_assert((63 - NS) + (NS - 1) * LS < NS * LS + (LS - 1) + NS, "lanes NS .. 63 stay inside the LDS copy");
+  const bool xlane = lane < NS;
+  rp = (const char*)(xlane ? th + lane : ta + (lane - NS));
+  rsb = xlane ? NS * 8u : LS * 8u;
+}
+template <int BATCH, int NS = 0>
 __device__ __forceinline__ void qp_residuals(const double* __restrict__ th, const double* ta, int lda,
                                              const double* tq, int ldq, const double* tb, const double* zs,
-                                             int ln, int n, int m, double eps, double s_own, double& F, double& Fc) {
+                                             int ln, int n, int m, double eps, double s_own, double& F, double& Fc,
+                                             const char* rp = nullptr, uint32_t rsb = 0) {
   const bool rg = ln < n, rh = ln >= n && ln < n + m;
   const int kh = ln - n;
-  const double* px = rg ? th + ln : (rh ? ta + kh : th);  // M column (θ) | A row
-  const int sx = rg ? n : (rh ? lda : 0);
-  double acc = MCPX_RES_INC ? dot_strided_inc<BATCH>(px, sx, zs, n, 0.0)   // M_ij x_j  |  A_kj x_j
-                            : dot_strided<BATCH, false>(px, sx, zs, n, 0.0);
+  double acc;
+  if constexpr (NS > 0) {
+    acc = dot_strided_inc_b<BATCH>(rp, rsb, zs, NS, 0.0);
+  } else {
+    const double* px = rg ? th + ln : (rh ? ta + kh : th);  // M column (θ) | A row
+    const int sx = rg ? n : (rh ? lda : 0);
+    acc = MCPX_RES_INC ? dot_strided_inc<BATCH>(px, sx, zs, n, 0.0)   // M_ij x_j  |  A_kj x_j
+                       : dot_strided<BATCH, false>(px, sx, zs, n, 0.0);
+  }
   const double acc_y = dot_strided<BATCH, true>(tq + (rg ? ln * ldq : 0), 1, zs + n, m, acc);  // − A_ki y_k
   if (rg) acc = acc_y;
   F = 0.0;
@@ -701,14 +731,70 @@ __device__ __forceinline__ void fmac_row_bcast_self(double& acc, double nl) {
 // `ta` / `lda`: the A block as in qp_residuals.  TWO (affine family): the B fragment
 // comes from the negated G-side coupling tq / ldq (−Q_ik) instead of A_ki, so the
 // entries are S_ij = P_ij + Σ_k (−Q_ik)·(R_kj·D_k⁻¹) — the oracle's chain for either family.
-template <int NT, bool TWO = false>
+// NC: the compile-time n of the caller (0: runtime n).  With NC = 16·NT no index clamp can fire
+// and the diagonal is a compile-time set of lanes and elements; that case takes the two
+// shortcuts below (MCPX_FORM_IMM), the same loads and the same additions as the general form.
+#ifndef MCPX_FORM_IMM
+#define MCPX_FORM_IMM 1
+#endif
+template <int NT, bool TWO = false, int NC = 0>
 __device__ __forceinline__ void qp_schur_form_2d(const double* __restrict__ th, const double* ta, int lda,
                                                  const double* sD, int ln, int n, int m, double tol,
                                                  d4 (&acc)[NT][NT], const double* tq = nullptr, int ldq = 0) {
   // lr ∈ [0, 3] made visible to the compiler (ln is opaque_lane in the Newton loop): with
   // compile-time (n, m) the range checks of the loads and masks below then fold away
   const int lr = (ln >> 4) & 3, lc = ln & 15;
-  {  // C = Mᵀ blocks: element (p = lr + 4r, q = lc) of tile (I, J) is M[16J+q][16I+p] = θ[(16I+p)·n + 16J+q]
+  if constexpr (MCPX_FORM_IMM && NC > 0 && NC == 16 * NT) {
+    // Every load is one per-lane element index plus a compile-time offset (global_load with an
+    // immediate offset; the general form spends ≈ 2 VALU per load on the clamped address).
+    const double* const pb = th + (lr * NC + lc);
+    double mv[NT][NT][4];
+#pragma unroll
+    for (int I = 0; I < NT; ++I)
+#pragma unroll
+      for (int J = 0; J < NT; ++J)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mv[I][J][r] = pb[(16 * I + 4 * r) * NC + 16 * J];
+    // + tol on the diagonal: only tiles I = J hold diagonal entries, element r in the lanes
+    // lc = lr + 4r, i.e. lanes 17·lr + 4r (lr = 0 .. 3).  One v_add_f64 per candidate under
+    // that constant EXEC mask; every other lane keeps its value untouched (−0.0 and NaN
+    // payloads included), where the general form spends a compare-and-select pair.
+    static_assert(NT <= 2, "operand list of the diagonal asm");
+    uint64_t save;
+#define MCPX_DIAG_0 " s_mov_b32 exec_lo, 0x00020001\n s_mov_b32 exec_hi, 0x00080004\n"  /* lanes 0, 17, 34, 51 */
+#define MCPX_DIAG_1 " s_mov_b32 exec_lo, 0x00200010\n s_mov_b32 exec_hi, 0x00800040\n"  /* 4, 21, 38, 55 */
+#define MCPX_DIAG_2 " s_mov_b32 exec_lo, 0x02000100\n s_mov_b32 exec_hi, 0x08000400\n"  /* 8, 25, 42, 59 */
+#define MCPX_DIAG_3 " s_mov_b32 exec_lo, 0x20001000\n s_mov_b32 exec_hi, 0x80004000\n"  /* 12, 29, 46, 63 */
+    // (s_nop 4 after the restore: no DPP within 5 wait states of an EXEC write)
+    if constexpr (NT == 2) {
+      asm volatile("s_mov_b64 %0, exec\n"
+                   MCPX_DIAG_0 " v_add_f64 %1, %1, %9\n v_add_f64 %5, %5, %9\n"
+                   MCPX_DIAG_1 " v_add_f64 %2, %2, %9\n v_add_f64 %6, %6, %9\n"
+                   MCPX_DIAG_2 " v_add_f64 %3, %3, %9\n v_add_f64 %7, %7, %9\n"
+                   MCPX_DIAG_3 " v_add_f64 %4, %4, %9\n v_add_f64 %8, %8, %9\n"
+                   " s_mov_b64 exec, %0\n s_nop 4"
+                   : "=&s"(save), "+v"(mv[0][0][0]), "+v"(mv[0][0][1]), "+v"(mv[0][0][2]), "+v"(mv[0][0][3]),
+                     "+v"(mv[1][1][0]), "+v"(mv[1][1][1]), "+v"(mv[1][1][2]), "+v"(mv[1][1][3])
+                   : "s"(tol));
+    } else {
+      asm volatile("s_mov_b64 %0, exec\n"
+                   MCPX_DIAG_0 " v_add_f64 %1, %1, %5\n" MCPX_DIAG_1 " v_add_f64 %2, %2, %5\n"
+                   MCPX_DIAG_2 " v_add_f64 %3, %3, %5\n" MCPX_DIAG_3 " v_add_f64 %4, %4, %5\n"
+                   " s_mov_b64 exec, %0\n s_nop 4"
+                   : "=&s"(save), "+v"(mv[0][0][0]), "+v"(mv[0][0][1]), "+v"(mv[0][0][2]), "+v"(mv[0][0][3])
+                   : "s"(tol));
+    }
+#undef MCPX_DIAG_0
+#undef MCPX_DIAG_1
+#undef MCPX_DIAG_2
+#undef MCPX_DIAG_3
+#pragma unroll
+    for (int I = 0; I < NT; ++I)
+#pragma unroll
+      for (int J = 0; J < NT; ++J)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[I][J][r] = mv[I][J][r];
+  } else {  // C = Mᵀ blocks: element (p = lr + 4r, q = lc) of tile (I, J) is M[16J+q][16I+p] = θ[(16I+p)·n + 16J+q]
     double mv[NT][NT][4];
 #pragma unroll
     for (int I = 0; I < NT; ++I)
@@ -1306,6 +1392,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
     }
   }
 
+  // the residual stream's per-lane pointer and stride, once per instance: C3's fast pass.  Not in
+  // pass 2 or the shared-matrix kernels, where the three registers raise the kernel's count
+  // (pass 2: 108 -> 110, shared fast pass: 89 -> 90); those keep the per-step form.
+  constexpr bool RHOIST = (MCPX_RES_HOIST != 0) & (MCPX_RES_INC != 0) & LDSA & !LDSM & (PASS == 1) & !SHARED;
+  const char* res_p = nullptr;
+  uint32_t res_sb = 0;
+  if constexpr (RHOIST) res_stream<NC, LDA>(th0, (const double*)sA, lane, res_p, res_sb);
+
   double eps = 1.0;                    // :67
   double kkt = __builtin_huge_val();   // :68
   int status = 0;                      // :69
@@ -1353,7 +1447,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
       // quotient-per-use form costs (8 of them in the Schur K-loop).
       double rw = 1.0, Di = 1.0, ryr = 0.0;
       if constexpr (SCH) {
-        qp_residuals<MCPX_RES_BATCH>(tm, ta, lda, tq, ldq, tb, zs, ln, n, m, eps, s, F, Fc);
+        qp_residuals<MCPX_RES_BATCH, (RHOIST ? NC : 0)>(tm, ta, lda, tq, ldq, tb, zs, ln, n, m, eps, s, F, Fc, res_p,
+                                                         res_sb);
         rhs = -F;
         if (rh) {  // eliminate δs_k (pivot w_k) and then δy_k (pivot D_k)
           w = zs[ln] + tol;
@@ -1390,7 +1485,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
         constexpr int NT = (NMAX + 15) / 16;
         if (spd_try) {  // S formed transposed on the matrix cores, Gauss-Jordan in that layout
           d4 acc4[NT][NT];
-          qp_schur_form_2d<NT, AFF>(tm, ta, lda, sD, ln, n, m, tol, acc4, tq, ldq);
+          qp_schur_form_2d<NT, AFF, NC>(tm, ta, lda, sD, ln, n, m, tol, acc4, tq, ldq);
           MCPX_STAMP(2);
           double acc[NT][NT][4];
 #pragma unroll
@@ -1420,7 +1515,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
           // ds_bpermute: no n×n LDS tile, so LDS (2 KB per wave) does not cap occupancy
           constexpr int NT = (NMAX + 15) / 16;
           d4 acc4[NT][NT];
-          qp_schur_form_2d<NT, AFF>(tm, ta, lda, sD, ln, n, m, tol, acc4, tq, ldq);
+          qp_schur_form_2d<NT, AFF, NC>(tm, ta, lda, sD, ln, n, m, tol, acc4, tq, ldq);
           schur_rows_from_2d<NT, NMAX>(acc4, ln, n, a);
           rhs = sB[ln];
           ok = lu_solve_rows<NMAX>(a, rhs, (NC > 0) ? opaque(NS) : NS, ln, dz);
