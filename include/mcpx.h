@@ -514,6 +514,66 @@ int mcpx_vjp_batch_shared_reduce_device(const mcpx_desc* desc, const double* the
                                         double* dvar, int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Grouped shared-matrix batches: G matrix blocks, each shared by a run of instances (several
+ * heads of a QP layer in one minibatch, G hypotheses with S sampled right-hand sides each, G plants
+ * under one MPC formulation).  Between the full-θ calls (one block per instance) and the shared
+ * calls (one block per batch), in ONE call at the batch's full occupancy.
+ *   theta_shared   G blocks: block g is mcpx_theta_shared_dim doubles at theta_shared + g·shared_ld,
+ *                  shared_ld >= shared_dim; the padding is never read;
+ *   group_offsets  G + 1 offsets in HOST memory (in the _device forms too: metadata, like desc):
+ *                  group g owns the instances [off[g], off[g+1]); off[0] = 0, off[G] = batch,
+ *                  non-decreasing (empty groups are allowed).  Read before the call returns; the
+ *                  library builds its device-side lookup (one int32 per instance) from it in a block
+ *                  of its own, in stream order;
+ *   theta_var      [b; ϕ] / [g; h] per instance, stride desc->theta_ld, as in the shared calls.
+ * Families: QP and affine (MCPX_FAMILY_NONLINEAR: MCPX_EINVAL).  MCPX_EINVAL also for NULL
+ * theta_shared or group_offsets with batch > 0, num_groups < 0 (or 0 with batch > 0), offsets that
+ * decrease or do not run from 0 to batch, shared_ld / dshared_ld < shared_dim, and the NULL outputs
+ * the shared twins reject.  num_groups is bounded by the batch and int32 only.  Warm starts, params,
+ * outputs, size limits, kernel selection, MCPX_ENODEV, MCPX_HOST_CHUNK / _BUFFERS / _SHARDS and
+ * num_devices are those of the shared twins; the host calls upload all G blocks once per device, and
+ * theta_var, the warm starts and the lookup go through the chunk pipeline.
+ * Contracts (bitwise):
+ *   solve   every mcpx_out field of instance b of group g is that of mcpx_solve_batch[_device] on
+ *           θ′_b = [block g ‖ var_b], which is also mcpx_solve_batch_shared* on group g alone;
+ *   vjp     dvar[b], status[b] are those of mcpx_vjp_batch_shared* on group g alone;
+ *   reduce  dshared + g·dshared_ld [shared_dim] and used[g] are those of mcpx_vjp_batch_shared_reduce*
+ *           on group g alone: chunks of MCPX_REDUCE_CHUNK instances counted from off[g], the same
+ *           inclusion rule, entries and fold; an empty group gives +0.0 throughout and used[g] = 0;
+ *           the padding of dshared is not written.  dvar / status: those of the grouped vjp.  The
+ *           bits do not depend on devices, shards (cut at chunk boundaries), host chunks, launch
+ *           geometry or MCPX_REDUCE_CAP_KB.  An empty batch needs no device in the host call.
+ * No grouped JVP, shared_dot, cond or fused solve+VJP entry: a grouped solve followed by a grouped
+ * vjp is the composed route.  Added under 2.2.0 without a version step, as the shared entries. */
+int mcpx_solve_batch_grouped(const mcpx_desc* desc, const double* theta_shared, int64_t shared_ld,
+                             int32_t num_groups, const int64_t* group_offsets, const double* theta_var,
+                             const double* x0, const double* y0, const double* s0, const mcpx_params* prm,
+                             int num_devices, mcpx_out* out);
+int mcpx_solve_batch_grouped_device(const mcpx_desc* desc, const double* theta_shared, int64_t shared_ld,
+                                    int32_t num_groups, const int64_t* group_offsets, const double* theta_var,
+                                    const double* x0, const double* y0, const double* s0, const mcpx_params* prm,
+                                    const mcpx_out* out, void* stream);
+int mcpx_vjp_batch_grouped(const mcpx_desc* desc, const double* theta_shared, int64_t shared_ld, int32_t num_groups,
+                           const int64_t* group_offsets, const double* x, const double* y, const double* s,
+                           const double* gx, const double* gy, const double* gs, int num_devices, double* dvar,
+                           int32_t* status);
+int mcpx_vjp_batch_grouped_device(const mcpx_desc* desc, const double* theta_shared, int64_t shared_ld,
+                                  int32_t num_groups, const int64_t* group_offsets, const double* x,
+                                  const double* y, const double* s, const double* gx, const double* gy,
+                                  const double* gs, double* dvar, int32_t* status, void* stream);
+int mcpx_vjp_batch_grouped_reduce(const mcpx_desc* desc, const double* theta_shared, int64_t shared_ld,
+                                  int32_t num_groups, const int64_t* group_offsets, const double* x,
+                                  const double* y, const double* s, const double* gx, const double* gy,
+                                  const double* gs, const uint8_t* skip, int num_devices, double* dshared,
+                                  int64_t dshared_ld, int64_t* used, double* dvar, int32_t* status);
+int mcpx_vjp_batch_grouped_reduce_device(const mcpx_desc* desc, const double* theta_shared, int64_t shared_ld,
+                                         int32_t num_groups, const int64_t* group_offsets, const double* x,
+                                         const double* y, const double* s, const double* gx, const double* gy,
+                                         const double* gs, const uint8_t* skip, double* dshared,
+                                         int64_t dshared_ld, int64_t* used, double* dvar, int32_t* status,
+                                         void* stream);
+
+/* ---------------------------------------------------------------------------
  * Nonlinear G/H — MCPX_FAMILY_NONLINEAR (BASELINE C4: games, src/game.jl).
  *
  * The reference compiles F!/∇F_z! from Symbolics expressions once per problem

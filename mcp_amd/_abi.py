@@ -121,6 +121,24 @@ JVP_SHARED_DOT_ARGTYPES = [C.POINTER(Desc), _P, _P, _P, _P, C.c_int32, _P, _P, C
 # (desc, theta_shared, x, y, s, n_partials, shared_dot, var_dot, zdot, status, stream)
 JVP_SHARED_DOT_DEVICE_ARGTYPES = [C.POINTER(Desc), _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P]
 
+# mcpx_*_batch_grouped[_device]: G matrix blocks, each shared by a run of instances.  In every call
+# (theta_shared, shared_ld, num_groups, group_offsets) stands where the shared twin has theta_shared;
+# group_offsets is a HOST array of G + 1 int64 in the device forms too.
+_GROUPS = [_P, C.c_int64, C.c_int32, _P]
+# (desc, groups…, theta_var, x0, y0, s0, prm, num_devices, out)
+SOLVE_GROUPED_ARGTYPES = [C.POINTER(Desc), *_GROUPS, _P, _P, _P, _P, C.POINTER(Params), C.c_int, C.POINTER(Out)]
+# (desc, groups…, theta_var, x0, y0, s0, prm, out, stream)
+SOLVE_GROUPED_DEVICE_ARGTYPES = [C.POINTER(Desc), *_GROUPS, _P, _P, _P, _P, C.POINTER(Params), C.POINTER(Out), _P]
+# (desc, groups…, x, y, s, gx, gy, gs, num_devices, dvar, status)
+VJP_GROUPED_ARGTYPES = [C.POINTER(Desc), *_GROUPS, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P]
+# (desc, groups…, x, y, s, gx, gy, gs, dvar, status, stream)
+VJP_GROUPED_DEVICE_ARGTYPES = [C.POINTER(Desc), *_GROUPS, _P, _P, _P, _P, _P, _P, _P, _P, _P]
+# (desc, groups…, x, y, s, gx, gy, gs, skip, num_devices, dshared, dshared_ld, used, dvar, status)
+VJP_GROUPED_REDUCE_ARGTYPES = [C.POINTER(Desc), *_GROUPS, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int64, _P, _P, _P]
+# (desc, groups…, x, y, s, gx, gy, gs, skip, dshared, dshared_ld, used, dvar, status, stream)
+VJP_GROUPED_REDUCE_DEVICE_ARGTYPES = [C.POINTER(Desc), *_GROUPS, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P,
+                                      _P]
+
 
 def make_params(tol=1e-4, max_inner_iters=20, max_outer_iters=50, tightening_rate=0.1,
                 loosening_rate=0.5, min_stepsize=1e-4, tau=0.995, decay=0.5,

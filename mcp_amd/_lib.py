@@ -37,7 +37,9 @@ EXPORTS = ("mcpx_version", "mcpx_last_error", "mcpx_default_params", "mcpx_theta
            "mcpx_vjp_batch_shared_device", "mcpx_jvp_batch_shared", "mcpx_jvp_batch_shared_device",
            "mcpx_solve_vjp_batch_shared_device", "mcpx_vjp_batch_shared_reduce",
            "mcpx_vjp_batch_shared_reduce_device", "mcpx_jvp_batch_shared_dot", "mcpx_jvp_batch_shared_dot_device",
-           "mcpx_cond_batch_shared", "mcpx_cond_batch_shared_device")
+           "mcpx_cond_batch_shared", "mcpx_cond_batch_shared_device",
+           "mcpx_solve_batch_grouped", "mcpx_solve_batch_grouped_device", "mcpx_vjp_batch_grouped",
+           "mcpx_vjp_batch_grouped_device", "mcpx_vjp_batch_grouped_reduce", "mcpx_vjp_batch_grouped_reduce_device")
 
 
 ABI_MAJOR = 2  # include/mcpx.h MCPX_VERSION / 10000
@@ -111,6 +113,14 @@ def lib():
     L.mcpx_jvp_batch_shared_dot.argtypes = _abi.JVP_SHARED_DOT_ARGTYPES
     L.mcpx_jvp_batch_shared_dot_device.restype = C.c_int
     L.mcpx_jvp_batch_shared_dot_device.argtypes = _abi.JVP_SHARED_DOT_DEVICE_ARGTYPES
+    for name, types in (("mcpx_solve_batch_grouped", _abi.SOLVE_GROUPED_ARGTYPES),
+                        ("mcpx_solve_batch_grouped_device", _abi.SOLVE_GROUPED_DEVICE_ARGTYPES),
+                        ("mcpx_vjp_batch_grouped", _abi.VJP_GROUPED_ARGTYPES),
+                        ("mcpx_vjp_batch_grouped_device", _abi.VJP_GROUPED_DEVICE_ARGTYPES),
+                        ("mcpx_vjp_batch_grouped_reduce", _abi.VJP_GROUPED_REDUCE_ARGTYPES),
+                        ("mcpx_vjp_batch_grouped_reduce_device", _abi.VJP_GROUPED_REDUCE_DEVICE_ARGTYPES)):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = types
     I32P = C.POINTER(C.c_int32)
     L.mcpx_module_load.restype = C.c_int
     L.mcpx_module_load.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]

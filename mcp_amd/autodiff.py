@@ -407,6 +407,68 @@ def solve_shared_torch(family: int, n: int, m: int, theta_shared, theta_var, *, 
     return SharedSolution(x, y, s, status, rec)
 
 
+def _grouped_autograd_fn():
+    import torch
+
+    class _SolveGroupedFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, theta_shared, theta_var, rec, family, n, m, sizes, skip_failed, params):
+            from .batch import solve_batch_grouped_device
+
+            out = solve_batch_grouped_device(family, n, m, theta_shared.detach().contiguous(),
+                                             theta_var.detach().contiguous(), sizes, **params)
+            ctx.save_for_backward(theta_shared.detach())
+            ctx.rec, ctx.cfg = rec, (family, n, m, sizes, skip_failed)  # (see _SolveSharedFn)
+            rec.out = out
+            ctx.mark_non_differentiable(out["status"])
+            return out["x"].clone(), out["y"].clone(), out["s"].clone(), out["status"]
+
+        @staticmethod
+        def backward(ctx, gx, gy, gs, _gstatus):
+            from .batch import vjp_batch_grouped_reduce_device
+
+            (theta_shared,) = ctx.saved_tensors
+            family, n, m, sizes, skip_failed = ctx.cfg
+            rec, out = ctx.rec, ctx.rec.out
+            B = out["status"].shape[0]
+            f = lambda t: None if t is None else t.to(torch.float64).reshape(B, -1).contiguous()
+            skip = (out["status"] != 0).to(torch.uint8) if skip_failed else None
+            dshared, used, dvar, st = vjp_batch_grouped_reduce_device(
+                family, n, m, theta_shared.contiguous(), out["x"], out["y"], out["s"], sizes, f(gx), f(gy), f(gs),
+                skip=skip)
+            rec.used, rec.sensitivity_status = used, st
+            return dshared, dvar, None, None, None, None, None, None, None
+
+    return _SolveGroupedFn
+
+
+_GROUPED_FN = None
+
+
+def solve_grouped_torch(family: int, n: int, m: int, theta_shared, theta_var, group_sizes, *,
+                        skip_failed: bool = True, **params) -> SharedSolution:
+    """solve_shared_torch for G sets of trainable matrices in one batch (several heads or layers of
+    an optimisation layer in one minibatch): theta_shared (G, shared_dim), theta_var (B, n + m),
+    group_sizes a host sequence of G ints summing to B — run g of instances uses block g.  Forward:
+    solve_batch_grouped_device.  Backward: one vjp_batch_grouped_reduce_device call —
+    theta_shared.grad[g] and theta_var.grad's rows are, bit for bit, what solve_shared_torch gives on
+    group g alone; `used` on the solution is (G,) after the backward pass."""
+    global _GROUPED_FN
+    if not (_is_torch(theta_shared) and theta_shared.is_cuda and _is_torch(theta_var) and theta_var.is_cuda):
+        raise ValueError("solve_grouped_torch needs HIP (cuda) tensors theta_shared and theta_var")
+    if theta_var.dim() != 2 or theta_var.shape[1] != n + m:
+        raise ValueError("theta_var must be a (B, n + m) tensor")
+    sizes = tuple(int(k) for k in group_sizes)
+    if theta_shared.dim() != 2 or theta_shared.shape[0] != len(sizes):
+        raise ValueError("theta_shared must be a (G, shared_dim) tensor with one row per group")
+    if _GROUPED_FN is None:
+        _GROUPED_FN = _grouped_autograd_fn()
+    rec = _BackwardRecord()
+    x, y, s, status = _GROUPED_FN.apply(theta_shared, theta_var, rec, int(family), int(n), int(m), sizes,
+                                        bool(skip_failed), dict(params))
+    return SharedSolution(x, y, s, status, rec)
+
+
 def solve_torch(mcp, θ, *, solver_type=None, **kwargs):
     """Differentiable batched solve on device: θ a (B, p) float64 HIP tensor
     (requires_grad allowed) → (x, y, s, status) with x, y, s differentiable

@@ -732,3 +732,213 @@ def vjp_batch_shared_reduce_device(family: int, n: int, m: int, theta_shared, x,
         C.byref(desc), sh, *ptrs, None if skip is None else skip.data_ptr(), _dev_f64(dshared, "dshared"),
         used.data_ptr(), _dev_f64(dvar, "dvar"), status.data_ptr(), C.c_void_p(st.cuda_stream)))
     return dshared, used, dvar, status
+
+
+# ---------------------------------------------------------------------------
+# grouped shared-matrix batches (include/mcpx.h mcpx_*_batch_grouped*): G matrix blocks, each shared
+# by a run of instances — between one block per instance (solve_batch) and one per batch (*_shared)
+
+
+def _group_offsets(group_sizes, B: int) -> np.ndarray:
+    """The G + 1 host offsets of `group_sizes` (G non-negative ints that sum to B)."""
+    sizes = np.asarray(list(group_sizes), dtype=np.int64).reshape(-1)
+    if sizes.size and sizes.min() < 0:
+        raise ValueError("group_sizes must be non-negative")
+    if int(sizes.sum()) != int(B):
+        raise ValueError(f"group_sizes sum to {int(sizes.sum())}, the batch has {int(B)} instances")
+    return np.concatenate([np.zeros(1, np.int64), np.cumsum(sizes, dtype=np.int64)])
+
+
+def _host_groups(family: int, n: int, m: int, theta_shared, G: int):
+    """(array, shared_ld) of a host (G, shared_dim) block array, or a 2-D view of a padded one."""
+    ds = _abi.theta_shared_dim(family, n, m)
+    a = np.asarray(theta_shared, dtype=np.float64)
+    if a.ndim != 2 or a.shape != (G, ds):
+        raise ValueError(f"theta_shared must be (G, shared_dim) = ({G}, {ds}), got {a.shape}")
+    if G > 1 and ds > 0 and a.strides[1] == 8 and a.strides[0] >= 8 * ds and a.strides[0] % 8 == 0:
+        return a, a.strides[0] // 8  # rows in place, padding and all
+    return np.ascontiguousarray(a), ds
+
+
+def _dev_groups(family: int, n: int, m: int, theta_shared, G: int):
+    """(pointer, shared_ld) of a device (G, shared_dim) float64 tensor or a padded 2-D view."""
+    import torch
+
+    ds = _abi.theta_shared_dim(family, n, m)
+    t = theta_shared
+    if not (t.is_cuda and t.dtype == torch.float64 and t.dim() == 2 and tuple(t.shape) == (G, ds)):
+        raise ValueError(f"theta_shared must be a (G, shared_dim) = ({G}, {ds}) float64 device tensor")
+    if G > 1 and ds > 0:
+        if not (t.stride(1) == 1 and t.stride(0) >= ds):
+            raise ValueError("theta_shared rows must be contiguous (a padded 2-D view is fine)")
+        return t.data_ptr(), t.stride(0)
+    if not t.is_contiguous():
+        raise ValueError("theta_shared must be contiguous")
+    return t.data_ptr(), ds
+
+
+def solve_batch_grouped(family: int, n: int, m: int, theta_shared, theta_var, group_sizes, *, x0=None, y0=None,
+                        s0=None, params=None, num_devices: int = 0, trace_len: int = 0, out: dict | None = None,
+                        **kw) -> dict:
+    """solve_batch for a batch of G runs of instances, each run sharing its matrices
+    (mcpx_solve_batch_grouped).  theta_shared: (G, shared_dim) or a padded 2-D view; theta_var:
+    (B, ≥ var_dim); group_sizes: G ints summing to B, run g takes the next group_sizes[g] instances
+    (0 allowed).  Every field equals solve_batch on the materialised θ′ bit for bit."""
+    theta_var = np.ascontiguousarray(theta_var, dtype=np.float64)
+    if theta_var.ndim == 1:
+        theta_var = theta_var[None, :]
+    B, ld = theta_var.shape
+    off = _group_offsets(group_sizes, B)
+    G = off.size - 1
+    sh, sld = _host_groups(family, n, m, theta_shared, G)
+    prm = _params(params, **kw)
+    conv = lambda a, k: None if a is None else np.ascontiguousarray(np.broadcast_to(a, (B, k)), dtype=np.float64)
+    x0, y0, s0 = conv(x0, n), conv(y0, m), conv(s0, m)
+    r, o = _host_out(B, n, m, trace_len, out)
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(ld))
+    check(lib().mcpx_solve_batch_grouped(C.byref(desc), _ptr(sh), int(sld), int(G), _ptr(off), _ptr(theta_var),
+                                         _ptr(x0), _ptr(y0), _ptr(s0), C.byref(prm), int(num_devices), C.byref(o)))
+    return r
+
+
+def solve_batch_grouped_device(family: int, n: int, m: int, theta_shared, theta_var, group_sizes,
+                               out: dict | None = None, *, x0=None, y0=None, s0=None, params=None,
+                               trace_len: int = 0, stream=None, **kw) -> dict:
+    """Device-tensor form (mcpx_solve_batch_grouped_device), enqueued on the current stream, no
+    synchronisation; group_sizes stays a host sequence."""
+    import torch
+
+    ok = lambda t: t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+    if not (ok(theta_var) and theta_var.dim() == 2):
+        raise ValueError("theta_var must be a contiguous (B, n + m) float64 device tensor")
+    B, ld = theta_var.shape
+    off = _group_offsets(group_sizes, B)
+    G = off.size - 1
+    sh, sld = _dev_groups(family, n, m, theta_shared, G)
+    if out is None:
+        out = alloc_device_outputs(B, n, m, theta_var.device, trace_len)
+    for t in (x0, y0, s0):
+        if t is not None and not ok(t):
+            raise ValueError("warm starts must be contiguous float64 device tensors")
+    dp = lambda t: None if t is None else t.data_ptr()
+    tl = 0 if out.get("alpha_trace") is None else out["alpha_trace"].shape[1]
+    o = _abi.Out(dp(out["x"]), dp(out["y"]), dp(out["s"]), dp(out["kkt_error"]), dp(out["eps"]),
+                 dp(out["outer_iters"]), dp(out["status"]), dp(out.get("newton_iters")),
+                 dp(out.get("active_mask")), dp(out.get("alpha_trace")), int(tl), 0, dp(out.get("fail_reason")))
+    prm = _params(params, **kw)
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(ld))
+    st = stream if stream is not None else torch.cuda.current_stream(theta_var.device)
+    check(lib().mcpx_solve_batch_grouped_device(C.byref(desc), sh, int(sld), int(G), _ptr(off), dp(theta_var), dp(x0),
+                                                dp(y0), dp(s0), C.byref(prm), C.byref(o),
+                                                C.c_void_p(st.cuda_stream)))
+    return out
+
+
+def vjp_batch_grouped(family: int, n: int, m: int, theta_shared, x, y, s, group_sizes, gx=None, gy=None, gs=None,
+                      num_devices: int = 0) -> tuple:
+    """vjp_batch_shared for a grouped batch (mcpx_vjp_batch_grouped): (dvar (B, n + m), status (B,)),
+    the bits of vjp_batch_shared on each group alone."""
+    B = _batch_of(np.atleast_2d(np.asarray(x)), np.atleast_2d(np.asarray(y)), n, m)
+    off = _group_offsets(group_sizes, B)
+    G = off.size - 1
+    sh, sld = _host_groups(family, n, m, theta_shared, G)
+    dv = _abi.theta_var_dim(family, n, m)
+    x, y, s = _host_f64(x, (B, n)), _host_f64(y, (B, m)), _host_f64(s, (B, m))
+    gx, gy, gs = _host_f64(gx, (B, n)), _host_f64(gy, (B, m)), _host_f64(gs, (B, m))
+    dvar = np.empty((B, dv))
+    st = np.empty(B, np.int32)
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(dv))
+    check(lib().mcpx_vjp_batch_grouped(C.byref(desc), _ptr(sh), int(sld), int(G), _ptr(off), _ptr(x), _ptr(y), _ptr(s),
+                                       _ptr(gx), _ptr(gy), _ptr(gs), int(num_devices), _ptr(dvar), _ptr(st)))
+    return dvar, st
+
+
+def vjp_batch_grouped_device(family: int, n: int, m: int, theta_shared, x, y, s, group_sizes, gx=None, gy=None,
+                             gs=None, dvar=None, status=None, stream=None):
+    """Device-tensor pullback of a grouped batch, enqueued on the current stream (no sync)."""
+    import torch
+
+    B = _batch_of(x, y, n, m)
+    off = _group_offsets(group_sizes, B)
+    G = off.size - 1
+    sh, sld = _dev_groups(family, n, m, theta_shared, G)
+    dv = _abi.theta_var_dim(family, n, m)
+    dev = theta_shared.device
+    if dvar is None:
+        dvar = torch.empty(B, dv, dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+    ptrs = [_dev_f64(t, k) for t, k in ((x, "x"), (y, "y"), (s, "s"), (gx, "gx"), (gy, "gy"), (gs, "gs"))]
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(dv))
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    check(lib().mcpx_vjp_batch_grouped_device(C.byref(desc), sh, int(sld), int(G), _ptr(off), *ptrs,
+                                              _dev_f64(dvar, "dvar"), status.data_ptr(), C.c_void_p(st.cuda_stream)))
+    return dvar, status
+
+
+def vjp_batch_grouped_reduce(family: int, n: int, m: int, theta_shared, x, y, s, group_sizes, gx=None, gy=None,
+                             gs=None, skip=None, num_devices: int = 0, want_dvar: bool = True) -> tuple:
+    """vjp_batch_grouped plus every group's gradient of its matrix block summed over the group
+    (mcpx_vjp_batch_grouped_reduce).  Returns (dshared (G, shared_dim), used (G,) int64, dvar
+    (B, n + m) or None, status (B,)); dshared[g] and used[g] are the bits of vjp_batch_shared_reduce
+    on group g alone (an empty group: +0.0 and 0)."""
+    B = _batch_of(np.atleast_2d(np.asarray(x)), np.atleast_2d(np.asarray(y)), n, m)
+    off = _group_offsets(group_sizes, B)
+    G = off.size - 1
+    sh, sld = _host_groups(family, n, m, theta_shared, G)
+    ds, dv = _abi.theta_shared_dim(family, n, m), _abi.theta_var_dim(family, n, m)
+    x, y, s = _host_f64(x, (B, n)), _host_f64(y, (B, m)), _host_f64(s, (B, m))
+    gx, gy, gs = _host_f64(gx, (B, n)), _host_f64(gy, (B, m)), _host_f64(gs, (B, m))
+    if skip is not None:
+        skip = np.ascontiguousarray(np.broadcast_to(np.asarray(skip) != 0, (B,)), dtype=np.uint8)
+    dshared = np.empty((G, ds))
+    used = np.zeros(max(G, 1), np.int64)
+    dvar = np.empty((B, dv)) if want_dvar else None
+    st = np.empty(B, np.int32)
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(dv))
+    check(lib().mcpx_vjp_batch_grouped_reduce(C.byref(desc), _ptr(sh), int(sld), int(G), _ptr(off), _ptr(x), _ptr(y),
+                                              _ptr(s), _ptr(gx), _ptr(gy), _ptr(gs), _ptr(skip), int(num_devices),
+                                              dshared.ctypes.data, int(ds), _ptr(used), _ptr(dvar), _ptr(st)))
+    return dshared, used[:G], dvar, st
+
+
+def vjp_batch_grouped_reduce_device(family: int, n: int, m: int, theta_shared, x, y, s, group_sizes, gx=None,
+                                    gy=None, gs=None, skip=None, dshared=None, used=None, dvar=None, status=None,
+                                    want_dvar: bool = True, stream=None):
+    """Device-tensor form, enqueued on the current stream (no sync).  Returns (dshared
+    (G, shared_dim), used (G,) int64, dvar (B, n + m) or None, status (B,) int32) tensors."""
+    import torch
+
+    B = _batch_of(x, y, n, m)
+    off = _group_offsets(group_sizes, B)
+    G = off.size - 1
+    sh, sld = _dev_groups(family, n, m, theta_shared, G)
+    ds, dv = _abi.theta_shared_dim(family, n, m), _abi.theta_var_dim(family, n, m)
+    dev = theta_shared.device
+    if dshared is None:
+        dshared = torch.empty(G, ds, dtype=torch.float64, device=dev)
+    if used is None:
+        used = torch.empty(G, dtype=torch.int64, device=dev)
+    if dvar is None and want_dvar:
+        dvar = torch.empty(B, dv, dtype=torch.float64, device=dev)
+    if status is None:
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+    if skip is not None:
+        if skip.dtype == torch.bool:
+            skip = skip.view(torch.uint8)
+        if not (skip.is_cuda and skip.dtype == torch.uint8 and skip.is_contiguous() and skip.numel() == B):
+            raise ValueError("skip must be a contiguous (B,) uint8 or bool device tensor")
+    if not (dshared.is_cuda and dshared.dtype == torch.float64 and tuple(dshared.shape) == (G, ds)
+            and (G <= 1 or ds == 0 or (dshared.stride(1) == 1 and dshared.stride(0) >= ds))):
+        raise ValueError("dshared must be a (G, shared_dim) float64 device tensor with contiguous rows")
+    if not (used.is_cuda and used.dtype == torch.int64 and used.is_contiguous() and used.numel() == G):
+        raise ValueError("used must be a contiguous (G,) int64 device tensor")
+    dld = dshared.stride(0) if G > 1 and ds > 0 else ds
+    ptrs = [_dev_f64(t, k) for t, k in ((x, "x"), (y, "y"), (s, "s"), (gx, "gx"), (gy, "gy"), (gs, "gs"))]
+    desc = _abi.Desc(int(family), int(n), int(m), 0, int(B), int(dv))
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    check(lib().mcpx_vjp_batch_grouped_reduce_device(
+        C.byref(desc), sh, int(sld), int(G), _ptr(off), *ptrs, None if skip is None else skip.data_ptr(),
+        dshared.data_ptr(), int(dld), used.data_ptr(), _dev_f64(dvar, "dvar"), status.data_ptr(),
+        C.c_void_p(st.cuda_stream)))
+    return dshared, used, dvar, status

@@ -30,9 +30,10 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "ipm_inst_wg.hip", "ipm_inst_wg_vr.hip", "ipm_inst_wg_gj.hip", "sens_inst_wg.hip", "ipm_inst_fused.hip",
     "ipm_inst_shared_spec.hip", "ipm_inst_shared_schur.hip", "theta_expand.hip",
     "sens_inst_vjp_shared.hip", "sens_inst_jvp_shared.hip", "sens_inst_wg_shared.hip", "ipm_inst_shared_fused.hip",
-    "shared_reduce.hip", "sens_inst_jvp_shared_dot.hip", "sens_inst_wg_shared_dot.hip", "mcpx_api.cpp")]
+    "shared_reduce.hip", "grouped_reduce.hip", "sens_inst_jvp_shared_dot.hip", "sens_inst_wg_shared_dot.hip", "mcpx_api.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, f) for f in ("ipm_kernel.h", "ipm_kernel_impl.hpp", "bcast_group.inc", "sens_kernel.h", "sens_kernel_impl.hpp",
-    "ipm_wg.h", "ipm_wg_impl.hpp", "lu_vr.hpp", "gj_vr.hpp", "sens_wg_impl.hpp", "wg_layout.h", "dev_pool.hpp")] + [
+    "ipm_wg.h", "ipm_wg_impl.hpp", "lu_vr.hpp", "gj_vr.hpp", "sens_wg_impl.hpp", "wg_layout.h", "dev_pool.hpp",
+    "shared_reduce_impl.hpp")] + [
     os.path.join(ROOT, "include", "mcpx.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

@@ -193,6 +193,62 @@ struct AsyncBuf {  // a cache block, released on the stream it was allocated on
   ~AsyncBuf() { dev_release(p, st); }
 };
 
+// Pinned host staging for the small tables a device-buffer call builds from host metadata (the
+// group lookup of mcpx_*_batch_grouped_device): the caller may free its metadata when the call
+// returns, so the copy to the device runs from a buffer of the library's.  A buffer is reused once
+// the event recorded after its last copy has completed; idle ones beyond kStageKeep are freed.
+constexpr size_t kStageKeep = 8;
+struct Stage {
+  void* p = nullptr;
+  size_t bytes = 0;
+  hipEvent_t done = nullptr;
+  bool busy = false;
+};
+std::mutex g_stage_mu;
+std::vector<Stage> g_stages;
+
+hipError_t stage_acquire(size_t bytes, void** p) {
+  *p = nullptr;
+  std::lock_guard<std::mutex> lock(g_stage_mu);
+  for (auto& s : g_stages)
+    if (!s.busy && s.bytes >= bytes && (!s.done || hipEventQuery(s.done) == hipSuccess)) {
+      s.busy = true;
+      *p = s.p;
+      return hipSuccess;
+    }
+  (void)hipGetLastError();  // hipErrorNotReady of a query is no error of this call
+  Stage s;
+  s.bytes = std::max<size_t>(bytes, 4096);
+  if (hipError_t e = hipHostMalloc(&s.p, s.bytes, hipHostMallocDefault); e != hipSuccess) return e;
+  s.busy = true;
+  g_stages.push_back(s);
+  *p = s.p;
+  return hipSuccess;
+}
+
+// After the last copy out of `p` was enqueued on `st`.
+void stage_release(void* p, hipStream_t st) {
+  if (!p) return;
+  std::lock_guard<std::mutex> lock(g_stage_mu);
+  size_t idle = 0;
+  for (auto& s : g_stages) {
+    if (s.p == p) {
+      if (!s.done) (void)hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
+      if (s.done) (void)hipEventRecord(s.done, st);
+      s.busy = false;
+    }
+    idle += s.busy ? 0 : 1;
+  }
+  for (auto it = g_stages.begin(); it != g_stages.end() && idle > kStageKeep;) {
+    if (it->busy || it->p == p || (it->done && hipEventQuery(it->done) != hipSuccess)) { ++it; continue; }
+    if (it->done) (void)hipEventDestroy(it->done);
+    (void)hipHostFree(it->p);
+    it = g_stages.erase(it);
+    --idle;
+  }
+  (void)hipGetLastError();
+}
+
 // The host-buffer pipeline's two streams and per-buffer events.  Creating streams per call
 // maps new hardware queues every time (≈10 ms per call: profiles/r02/host_pipeline_trace.txt),
 // so they come from a process-wide free list per device: a call takes one Pipe and gives

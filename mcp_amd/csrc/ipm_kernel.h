@@ -54,6 +54,11 @@ struct KernelArgs {
   // [vec(M); vec(A)] block of every instance, [b; ϕ] of instance i is at theta_var + i·var_ld
   const double* theta_var;
   int64_t var_ld;
+  // grouped shared-matrix batches (mcpx_solve_batch_grouped*, the SHARED kernels; NULL otherwise):
+  // instance i reads the block at theta + group_map[i]·shared_ld.  Last: the kernels of generated
+  // modules never look past var_ld.
+  const int32_t* group_map;
+  int64_t shared_ld;
 };
 
 // Launchers of the register-resident solver: one 64-lane wave (= one
@@ -86,5 +91,9 @@ hipError_t launch_ipm_shared_fused_vjp(int n, int m, const KernelArgs& a, int64_
 // for i < nb, j < ds + dv; out_ld even and `out` 16-byte aligned (vector stores).
 hipError_t launch_theta_expand(const double* shared, const double* var, int64_t var_ld, double* out, int64_t out_ld,
                                int64_t ds, int64_t dv, int64_t nb, hipStream_t st);
+// The same for a grouped batch: instance i's head is the block at shared + map[i]·shared_ld.
+hipError_t launch_theta_expand_grouped(const double* shared, int64_t shared_ld, const int32_t* map, const double* var,
+                                       int64_t var_ld, double* out, int64_t out_ld, int64_t ds, int64_t dv,
+                                       int64_t nb, hipStream_t st);
 
 }  // namespace mcpx

@@ -1305,8 +1305,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
   const int64_t inst = blockIdx.x;
   const int n0 = NC ? NC : args.n, m0 = MC ? MC : args.m;
   const double* th0_;
-  if constexpr (SHARED) th0_ = args.theta;  // the one [vec(M); vec(A)] block
-  else th0_ = args.theta + inst * args.theta_ld;
+  if constexpr (SHARED) {
+    th0_ = args.theta;  // the one [vec(M); vec(A)] block, or (grouped batch) the block of this instance's group
+    if (args.group_map) th0_ += (int64_t)args.group_map[inst] * args.shared_ld;  // one scalar load per instance
+  } else th0_ = args.theta + inst * args.theta_ld;
   const double* const th0 = th0_;
   const double tol = args.tol;
   if constexpr (AFF) {  // −Qᵀ (row i at sQ[i·(m+1)]), then −h, −g

@@ -310,6 +310,80 @@ hipError_t launch(int nmax, const mcpx::KernelArgs& a, int64_t nb, hipStream_t s
 // uint64 words of one instance's active-set mask: ⌈m/64⌉, at least 1 (include/mcpx.h)
 inline int64_t mask_words(int m) { return m > 64 ? (m + 63) / 64 : 1; }
 
+// ---- grouped shared-matrix batches (mcpx_*_batch_grouped*) -------------------------------------
+
+// What a grouped call derives from its host metadata, once, before any launch.
+struct GroupTable {
+  int64_t G = 0;
+  std::vector<int32_t> map;              // [B]: instance → group, the kernels' lookup
+  std::vector<double> packed;            // host entries, padded blocks: the G blocks at stride shared_dim
+  std::vector<mcpx::GroupChunk> chunks;  // reduce entries: chunks of MCPX_REDUCE_CHUNK counted from each off[g]
+  std::vector<int64_t> cbase;            // reduce entries, [G + 1]: group g owns chunks [cbase[g], cbase[g + 1])
+};
+
+// The argument checks of the grouped entries after the descriptor's (ds: mcpx_theta_shared_dim).
+int check_groups(const mcpx_desc* d, const double* shared, int64_t shared_ld, int32_t G, const int64_t* off,
+                 int64_t ds) {
+  if (G < 0) return fail(MCPX_EINVAL, "negative num_groups");
+  if (shared_ld < ds) return fail(MCPX_EINVAL, "shared_ld %lld < shared dimension %lld", (long long)shared_ld, (long long)ds);
+  if (d->batch > 0 && (G == 0 || !shared || !off))
+    return fail(MCPX_EINVAL, "a non-empty grouped batch needs num_groups >= 1, theta_shared and group_offsets");
+  if (off) {
+    if (off[0] != 0 || off[G] != d->batch)
+      return fail(MCPX_EINVAL, "group_offsets must run from 0 to batch (%lld): got %lld .. %lld", (long long)d->batch,
+                  (long long)off[0], (long long)off[G]);
+    for (int32_t g = 0; g < G; ++g)
+      if (off[g + 1] < off[g]) return fail(MCPX_EINVAL, "group_offsets decrease at group %d", g);
+  }
+  return MCPX_OK;
+}
+
+// The tables of a checked, non-empty grouped call.  `pack` (host entries): the blocks for upload.
+void build_groups(const mcpx_desc* d, const double* shared, int64_t shared_ld, int32_t G, const int64_t* off,
+                  int64_t ds, bool pack, bool reduce, GroupTable* t) {
+  t->G = G;
+  t->map.resize((size_t)d->batch);
+  for (int32_t g = 0; g < G; ++g) std::fill(t->map.begin() + off[g], t->map.begin() + off[g + 1], g);
+  if (pack && shared_ld != ds) {
+    t->packed.resize((size_t)(G * ds));
+    for (int32_t g = 0; g < G; ++g) std::copy(shared + g * shared_ld, shared + g * shared_ld + ds, t->packed.begin() + g * ds);
+  }
+  if (!reduce) return;
+  t->cbase.assign((size_t)G + 1, 0);
+  for (int32_t g = 0; g < G; ++g) {
+    for (int64_t b = off[g]; b < off[g + 1]; b += MCPX_REDUCE_CHUNK)
+      t->chunks.push_back(mcpx::GroupChunk{b, (int32_t)std::min<int64_t>(MCPX_REDUCE_CHUNK, off[g + 1] - b), g});
+    t->cbase[(size_t)g + 1] = (int64_t)t->chunks.size();
+  }
+}
+
+// The tables of a device-buffer call on the device: one block of the cache, filled on `st` from a
+// pinned staging buffer of the library's (the caller's offsets are not read after the call returns).
+struct DevGroups {
+  AsyncBuf<char> blk;
+  const int32_t* map = nullptr;
+  const mcpx::GroupChunk* chunks = nullptr;
+  const int64_t* cbase = nullptr;
+  hipError_t upload(const GroupTable& t, hipStream_t st) {
+    const size_t nm = (t.map.size() * sizeof(int32_t) + 15) & ~(size_t)15;
+    const size_t nc = t.chunks.size() * sizeof(mcpx::GroupChunk), nb = t.cbase.size() * sizeof(int64_t);
+    const size_t bytes = nm + nc + nb;
+    hipError_t e = blk.alloc(bytes, st);
+    if (e != hipSuccess) return e;
+    void* h = nullptr;
+    if ((e = stage_acquire(bytes, &h)) != hipSuccess) return e;
+    std::memcpy(h, t.map.data(), t.map.size() * sizeof(int32_t));
+    if (nc) std::memcpy((char*)h + nm, t.chunks.data(), nc);
+    if (nb) std::memcpy((char*)h + nm + nc, t.cbase.data(), nb);
+    e = hipMemcpyAsync(blk.p, h, bytes, hipMemcpyHostToDevice, st);
+    stage_release(h, st);
+    map = (const int32_t*)blk.p;
+    chunks = (const mcpx::GroupChunk*)(blk.p + nm);
+    cbase = (const int64_t*)(blk.p + nm + nc);
+    return e;
+  }
+};
+
 // Per-instance pointers of chunk [b0, b0 + nb) into the kernel args.
 void set_chunk(mcpx::KernelArgs& a, const mcpx_desc* d, const double* theta, const double* x0, const double* y0,
                const double* s0, const mcpx_out* o, int64_t b0) {
@@ -466,9 +540,12 @@ int64_t expand_cap() {
 //     in one block of the device cache, each solved by the kernels of the full-θ call before the
 //     next slice overwrites it (stream order).
 // Both give the bits of launch_chunks on the materialised θ′.
+// `gmap` (mcpx_solve_batch_grouped*): a grouped batch — instance i's block is shared + gmap[i]·shared_ld;
+// the map moves with the other per-instance pointers, and a slice may straddle group boundaries.
 int launch_shared_chunks(const mcpx_desc* d, const double* shared, const double* var, const double* x0,
                          const double* y0, const double* s0, const mcpx_out* o, mcpx::KernelArgs a,
-                         const SolvePlan& plan, hipStream_t st) {
+                         const SolvePlan& plan, hipStream_t st, const int32_t* gmap = nullptr,
+                         int64_t shared_ld = 0) {
   const int n = d->n, m = d->m;
   if (a.family == MCPX_FAMILY_QP && a.solver == MCPX_LINSOLVE_SCHUR && !plan.wg) {
     for (int64_t b0 = 0; b0 < d->batch; b0 += wg::kChunk) {
@@ -478,6 +555,8 @@ int launch_shared_chunks(const mcpx_desc* d, const double* shared, const double*
       a.var_ld = d->theta_ld;
       a.theta = shared;
       a.theta_ld = 0;
+      a.group_map = gmap ? gmap + b0 : nullptr;
+      a.shared_ld = shared_ld;
       hipError_t e = specialized_enabled() ? mcpx::launch_ipm_shared_spec(n, m, a, nb, st) : hipErrorNotFound;
       if (e == hipErrorNotFound) e = mcpx::launch_ipm_shared_schur(plan.nmax, a, nb, st);
       HIP_TRY(e);
@@ -497,7 +576,9 @@ int launch_shared_chunks(const mcpx_desc* d, const double* shared, const double*
   for (int64_t b0 = 0; b0 < d->batch && rc == MCPX_OK; b0 += slice) {
     dd.batch = std::min(slice, d->batch - b0);
     const hipError_t e =
-        mcpx::launch_theta_expand(shared, var + b0 * d->theta_ld, d->theta_ld, blk, ld, ds, dv, dd.batch, st);
+        gmap ? mcpx::launch_theta_expand_grouped(shared, shared_ld, gmap + b0, var + b0 * d->theta_ld, d->theta_ld, blk,
+                                                 ld, ds, dv, dd.batch, st)
+             : mcpx::launch_theta_expand(shared, var + b0 * d->theta_ld, d->theta_ld, blk, ld, ds, dv, dd.batch, st);
     if (e != hipSuccess) {
       rc = fail(MCPX_EHIP, "theta expansion launch failed: %s", hipGetErrorString(e));
       break;
@@ -540,9 +621,11 @@ int64_t host_chunk() {
 // `shared` (mcpx_solve_batch_shared): the one matrix block of a shared-matrix batch, uploaded
 // once ahead of the first chunk; `theta` is then the per-instance block (stride d->theta_ld)
 // and the only part of θ′ that goes through the rotating buffers.
+// `groups` (mcpx_solve_batch_grouped): `shared` is then its G blocks, packed (stride shared_dim), all
+// uploaded once, and each chunk's slice of the instance → group map goes up with its θ.
 int solve_shard(int dev, const mcpx_desc* d, const double* shared, const double* theta, const double* x0,
                 const double* y0, const double* s0, const mcpx::KernelArgs& a, const SolvePlan& plan, mcpx_out* o,
-                int64_t b0, int64_t nb) {
+                int64_t b0, int64_t nb, const GroupTable* groups = nullptr) {
   HIP_TRY(hipSetDevice(dev));
   int rc = check_device(dev);
   if (rc) return rc;
@@ -558,7 +641,7 @@ int solve_shard(int dev, const mcpx_desc* d, const double* shared, const double*
   hipStream_t cs = P->comp, us = P->up;
   AsyncBuf<double> th[kMaxHostBufs], wx[kMaxHostBufs], wy[kMaxHostBufs], ws[kMaxHostBufs];
   AsyncBuf<double> sh, x, y, s, kkt, eps;
-  AsyncBuf<int32_t> outer, status, newton;
+  AsyncBuf<int32_t> outer, status, newton, gm[kMaxHostBufs];
   AsyncBuf<uint64_t> am;
   AsyncBuf<uint8_t> tr, fr;
   // declared after the buffers, so it runs before their (stream-ordered) frees on every
@@ -576,11 +659,13 @@ int solve_shard(int dev, const mcpx_desc* d, const double* shared, const double*
     if (x0) HIP_TRY(wx[k].alloc((size_t)ch * n, cs));
     if (y0) HIP_TRY(wy[k].alloc((size_t)ch * m, cs));
     if (s0) HIP_TRY(ws[k].alloc((size_t)ch * m, cs));
+    if (groups) HIP_TRY(gm[k].alloc((size_t)ch, cs));
   }
   const int64_t ds = shared ? mcpx_theta_shared_dim(d->family, n, m) : 0;
+  const int64_t nsh = groups ? groups->G * ds : ds;  // doubles of the matrix block(s)
   // the last instance of a chunk of the per-instance block: its own doubles, not the stride
   const int64_t tail = shared ? mcpx_theta_var_dim(d->family, n, m) : ld;
-  if (shared) HIP_TRY(sh.alloc((size_t)std::max<int64_t>(ds, 1), cs));
+  if (shared) HIP_TRY(sh.alloc((size_t)std::max<int64_t>(nsh, 1), cs));
   HIP_TRY(x.alloc((size_t)nb * n, cs)); HIP_TRY(y.alloc((size_t)nb * m, cs)); HIP_TRY(s.alloc((size_t)nb * m, cs));
   HIP_TRY(kkt.alloc(nb, cs)); HIP_TRY(eps.alloc(nb, cs)); HIP_TRY(outer.alloc(nb, cs));
   HIP_TRY(status.alloc(nb, cs));
@@ -596,7 +681,7 @@ int solve_shard(int dev, const mcpx_desc* d, const double* shared, const double*
   HIP_TRY(hipEventRecord(P->consumed[0], cs));
   HIP_TRY(hipStreamWaitEvent(us, P->consumed[0], 0));
   // the shared block: once, on the upload stream ahead of chunk 0 (whose event covers it)
-  if (shared && ds > 0) HIP_TRY(hipMemcpyAsync(sh.p, shared, sizeof(double) * (size_t)ds, hipMemcpyHostToDevice, us));
+  if (shared && nsh > 0) HIP_TRY(hipMemcpyAsync(sh.p, shared, sizeof(double) * (size_t)nsh, hipMemcpyHostToDevice, us));
   for (int64_t c0 = 0, ci = 0; c0 < nb; c0 += ch, ++ci) {
     const int k = (int)(ci % nbuf);
     const int64_t cn = std::min(ch, nb - c0), g0 = b0 + c0;
@@ -606,6 +691,8 @@ int solve_shard(int dev, const mcpx_desc* d, const double* shared, const double*
     if (x0) HIP_TRY(hipMemcpyAsync(wx[k].p, x0 + g0 * n, sizeof(double) * cn * n, hipMemcpyHostToDevice, us));
     if (y0) HIP_TRY(hipMemcpyAsync(wy[k].p, y0 + g0 * m, sizeof(double) * cn * m, hipMemcpyHostToDevice, us));
     if (s0) HIP_TRY(hipMemcpyAsync(ws[k].p, s0 + g0 * m, sizeof(double) * cn * m, hipMemcpyHostToDevice, us));
+    if (groups)
+      HIP_TRY(hipMemcpyAsync(gm[k].p, groups->map.data() + g0, sizeof(int32_t) * cn, hipMemcpyHostToDevice, us));
     HIP_TRY(hipEventRecord(P->copied[k], us));
     HIP_TRY(hipStreamWaitEvent(cs, P->copied[k], 0));
     mcpx_out od{};
@@ -617,7 +704,7 @@ int solve_shard(int dev, const mcpx_desc* d, const double* shared, const double*
     od.fail_reason = fr.p ? fr.p + c0 : nullptr;
     mcpx_desc dd = *d;
     dd.batch = cn;
-    rc = shared ? launch_shared_chunks(&dd, sh.p, th[k].p, wx[k].p, wy[k].p, ws[k].p, &od, a, plan, cs)
+    rc = shared ? launch_shared_chunks(&dd, sh.p, th[k].p, wx[k].p, wy[k].p, ws[k].p, &od, a, plan, cs, gm[k].p, ds)
                 : launch_chunks(&dd, th[k].p, wx[k].p, wy[k].p, ws[k].p, &od, a, plan, cs);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(P->consumed[k], cs));
@@ -776,6 +863,7 @@ mcpx::SensArgs sens_chunk(mcpx::SensArgs a, bool jvp, int64_t b0) {
   if (a.gs) a.gs += b0 * m;
   if (a.theta_dot) a.theta_dot += b0 * a.n_partials * a.p;
   if (a.status) a.status += b0;
+  if (a.group_map) a.group_map += b0;
   return a;
 }
 
@@ -828,14 +916,16 @@ int launch_sens(bool jvp, const mcpx_desc* d, const mcpx::SensArgs& a, const Sen
 // A shared-matrix call (plan.split) uploads its one matrix block, no per-instance θ, and brings
 // back a.p = n + m doubles per instance (the VJP; rcond: one double).  plan.dot: the one
 // [K × shared_dim] block of matrix tangents goes up once as well.
+// `groups` (mcpx_vjp_batch_grouped): a.theta is the G packed blocks, all uploaded, with the shard's
+// slice of the instance → group map.
 int sens_shard(bool jvp, int dev, const mcpx_desc* d, const mcpx::SensArgs& a, const SensPlan& plan, int64_t b0,
-               int64_t nb) {
+               int64_t nb, const GroupTable* groups = nullptr) {
   HIP_TRY(hipSetDevice(dev));
   int rc = check_device(dev);
   if (rc) return rc;
   const int n = d->n, m = d->m;
   DevBuf<double> th, dx, dy, ds, dgx, dgy, dgs, dtd, dsd, dout;
-  DevBuf<int32_t> dst;
+  DevBuf<int32_t> dst, dmap;
   auto up = [&](DevBuf<double>& b, const double* h, size_t per) -> hipError_t {
     if (!h || !per || !nb) return hipSuccess;
     hipError_t e = b.alloc((size_t)nb * per);
@@ -843,8 +933,13 @@ int sens_shard(bool jvp, int dev, const mcpx_desc* d, const mcpx::SensArgs& a, c
   };
   if (plan.split) {
     const int64_t ds = mcpx_theta_shared_dim(d->family, n, m);
-    HIP_TRY(th.alloc((size_t)std::max<int64_t>(ds, 1)));
-    if (ds > 0) HIP_TRY(hipMemcpy(th.p, a.theta, sizeof(double) * (size_t)ds, hipMemcpyHostToDevice));
+    const int64_t nsh = groups ? groups->G * ds : ds;
+    HIP_TRY(th.alloc((size_t)std::max<int64_t>(nsh, 1)));
+    if (nsh > 0) HIP_TRY(hipMemcpy(th.p, a.theta, sizeof(double) * (size_t)nsh, hipMemcpyHostToDevice));
+    if (groups && nb) {
+      HIP_TRY(dmap.alloc((size_t)nb));
+      HIP_TRY(hipMemcpy(dmap.p, groups->map.data() + b0, sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice));
+    }
     const size_t nsd = plan.dot ? (size_t)a.n_partials * (size_t)ds : 0;
     if (nsd) {
       HIP_TRY(dsd.alloc(nsd));
@@ -875,6 +970,8 @@ int sens_shard(bool jvp, int dev, const mcpx_desc* d, const mcpx::SensArgs& a, c
   // an empty output (p = 0, or K = 0) still needs a valid base pointer
   da.out = dout.p ? dout.p : (double*)th.p;
   da.status = dst.p;
+  da.group_map = dmap.p;
+  da.shared_ld = groups ? mcpx_theta_shared_dim(d->family, n, m) : 0;
   if ((rc = launch_sens(jvp, &dd, da, plan, nullptr))) {
     (void)hipDeviceSynchronize();  // nothing may still run on the buffers freed on return
     return rc;
@@ -1264,6 +1361,265 @@ int prepare_shared(const mcpx_desc* d, const double* shared, const double* var, 
   return MCPX_OK;
 }
 
+// ---- the grouped entries -----------------------------------------------------------------------
+
+// What the grouped entries take in the shared block's place.
+struct GroupCall {
+  const double* shared;
+  int64_t shared_ld;
+  int32_t G;
+  const int64_t* off;
+};
+
+// mcpx_solve_batch_grouped[_device]: the checks of the shared solve, then the groups'.
+int prepare_grouped(const mcpx_desc* d, const GroupCall& g, const double* var, const mcpx_params* prm,
+                    const mcpx_out* o, mcpx::KernelArgs* a, SolvePlan* plan, bool* empty) {
+  int rc = prepare(d, prm, a, plan, nullptr, true);
+  if (rc) return rc;
+  if ((rc = check_groups(d, g.shared, g.shared_ld, g.G, g.off, mcpx_theta_shared_dim(d->family, d->n, d->m)))) return rc;
+  if (!outputs_ok(o)) return fail(MCPX_EINVAL, "required output arrays missing");
+  *empty = d->batch == 0;
+  if (!*empty && !var) return fail(MCPX_EINVAL, "theta_var is NULL");
+  return MCPX_OK;
+}
+
+// The split pullback's preparation and checks for a grouped call.
+int prepare_grouped_sens(const mcpx_desc* d, const GroupCall& g, mcpx::SensArgs* a, SensPlan* plan) {
+  int rc = prepare_sens(d, a, plan, kVjp, nullptr, true);
+  if (rc) return rc;
+  return check_groups(d, g.shared, g.shared_ld, g.G, g.off, mcpx_theta_shared_dim(d->family, d->n, d->m));
+}
+
+int grouped_vjp_device(const mcpx_desc* d, const GroupCall& g, mcpx::SensArgs a, void* stream) {
+  SensPlan plan;
+  int rc;
+  if ((rc = prepare_grouped_sens(d, g, &a, &plan))) return rc;
+  if ((rc = sens_inputs_ok(d, a)) || d->batch == 0) return rc;
+  int dev = 0;
+  if ((rc = current_device(&dev))) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  GroupTable t;
+  build_groups(d, g.shared, g.shared_ld, g.G, g.off, 0, false, false, &t);
+  DevGroups dg;
+  HIP_TRY(dg.upload(t, st));
+  a.group_map = dg.map;
+  a.shared_ld = g.shared_ld;
+  if (!a.x) a.x = a.theta;
+  if (!a.y) a.y = a.theta;
+  if (!a.s) a.s = a.theta;
+  return launch_sens(false, d, a, plan, st);
+}
+
+int grouped_vjp_host(const mcpx_desc* d, const GroupCall& g, mcpx::SensArgs a, int num_devices) {
+  SensPlan plan;
+  int rc;
+  if ((rc = prepare_grouped_sens(d, g, &a, &plan))) return rc;
+  if ((rc = sens_inputs_ok(d, a)) || d->batch == 0) return rc;
+  GroupTable t;
+  build_groups(d, g.shared, g.shared_ld, g.G, g.off, mcpx_theta_shared_dim(d->family, d->n, d->m), true, false, &t);
+  if (!t.packed.empty()) a.theta = t.packed.data();
+  return run_shards(num_devices, d->batch, [&](int dev, int64_t b0, int64_t nb) {
+    return sens_shard(false, dev, d, a, plan, b0, nb, &t);
+  });
+}
+
+// The grouped counterpart of launch_shared_reduce: the split pullback of `a` (device pointers whose
+// element 0 is instance inst0; a.group_map / a.shared_ld set), then the partials of the chunks
+// [c_lo, c_hi) of `t`, whose rows sit at dchunks[c − c_lo].  hpart == NULL: folded on the device into
+// dshared / used (zeroed by the caller; dcbase: t.cbase on the device).  Otherwise every chunk's
+// partial and count go to hpart [· × ds] / hcount at its chunk index of the whole batch.
+int launch_grouped_reduce(const mcpx_desc* d, mcpx::SensArgs a, const SensPlan& plan, const uint8_t* skip,
+                          const GroupTable& t, const mcpx::GroupChunk* dchunks, const int64_t* dcbase, int64_t c_lo,
+                          int64_t c_hi, int64_t inst0, double* dshared, int64_t dshared_ld, int64_t* used, double* hpart,
+                          int64_t* hcount, hipStream_t st) {
+  const int n = d->n, m = d->m;
+  const int64_t B = d->batch, ds = mcpx_theta_shared_dim(d->family, n, m), nch = c_hi - c_lo;
+  const int64_t portion = std::max<int64_t>(1, std::min(nch, reduce_partial_cap() / (std::max<int64_t>(ds, 1) * 8)));
+  AsyncBuf<double> own_dvar, part;
+  AsyncBuf<int32_t> own_status;
+  AsyncBuf<int64_t> count;
+  if (!a.out) {
+    HIP_TRY(own_dvar.alloc((size_t)B * (n + m), st));
+    a.out = own_dvar.p;
+  }
+  if (!a.status) {
+    HIP_TRY(own_status.alloc((size_t)B, st));
+    a.status = own_status.p;
+  }
+  HIP_TRY(part.alloc((size_t)(portion * std::max<int64_t>(ds, 1)), st));
+  HIP_TRY(count.alloc((size_t)portion, st));
+  if (const int rc = launch_sens(false, d, a, plan, st)) return rc;
+  mcpx::GroupReduceArgs r{};
+  r.r.x = a.x;
+  r.r.y = a.y;
+  r.r.dvar = a.out;
+  r.r.status = a.status;
+  r.r.skip = skip;
+  r.r.part = part.p;
+  r.r.count = count.p;
+  r.r.batch = B;
+  r.r.ds = ds;
+  r.r.n = n;
+  r.r.m = m;
+  r.r.family = d->family;
+  r.chunks = dchunks;
+  r.inst0 = inst0;
+  for (int64_t c0 = c_lo; c0 < c_hi; c0 += portion) {  // a portion may end inside a group: its chain goes on
+    const int64_t nc = std::min(portion, c_hi - c0);
+    r.r.chunk0 = c0 - c_lo;
+    HIP_TRY(mcpx::launch_grouped_reduce_partial(r, nc, st));
+    if (!hpart) {
+      HIP_TRY(mcpx::launch_grouped_reduce_fold(part.p, count.p, c0, nc, dcbase, t.chunks[(size_t)c0].group,
+                                               (int64_t)t.chunks[(size_t)(c0 + nc - 1)].group + 1, ds, dshared,
+                                               dshared_ld, used, st));
+    } else {  // stream-ordered: both copies are done before the next portion's kernel starts
+      if (ds > 0)
+        HIP_TRY(hipMemcpyAsync(hpart + c0 * ds, part.p, sizeof(double) * (size_t)(nc * ds), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(hcount + c0, count.p, sizeof(int64_t) * (size_t)nc, hipMemcpyDeviceToHost, st));
+    }
+  }
+  return MCPX_OK;
+}
+
+// What the grouped reduce entries take beyond a grouped pullback.
+struct GroupReduceCall {
+  const uint8_t* skip;
+  double* dshared;
+  int64_t dshared_ld;
+  int64_t* used;
+};
+
+int grouped_reduce_checks(const mcpx_desc* d, const GroupCall& g, const GroupReduceCall& c, mcpx::SensArgs* a,
+                          SensPlan* plan) {
+  int rc;
+  if ((rc = prepare_grouped_sens(d, g, a, plan))) return rc;
+  if (c.dshared_ld < mcpx_theta_shared_dim(d->family, d->n, d->m))
+    return fail(MCPX_EINVAL, "dshared_ld %lld < shared dimension", (long long)c.dshared_ld);
+  if (!c.dshared || !c.used) return fail(MCPX_EINVAL, "dshared and used must be non-NULL");
+  if (d->batch > 0 && ((d->n > 0 && !a->x) || (d->m > 0 && (!a->y || !a->s))))
+    return fail(MCPX_EINVAL, "solution arrays x/y/s must be non-NULL");
+  return MCPX_OK;
+}
+
+int grouped_reduce_device(const mcpx_desc* d, const GroupCall& g, mcpx::SensArgs a, const GroupReduceCall& c,
+                          void* stream) {
+  SensPlan plan;
+  int rc;
+  if ((rc = grouped_reduce_checks(d, g, c, &a, &plan))) return rc;
+  int dev = 0;
+  if ((rc = current_device(&dev))) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  const int64_t ds = mcpx_theta_shared_dim(d->family, d->n, d->m);
+  // every group's sum starts from +0.0 and 0: empty groups keep them, the folds go on from them
+  HIP_TRY(mcpx::launch_grouped_reduce_zero(c.dshared, c.dshared_ld, ds, g.G, c.used, st));
+  if (d->batch == 0) return MCPX_OK;
+  GroupTable t;
+  build_groups(d, g.shared, g.shared_ld, g.G, g.off, ds, false, true, &t);
+  DevGroups dg;
+  HIP_TRY(dg.upload(t, st));
+  a.group_map = dg.map;
+  a.shared_ld = g.shared_ld;
+  if (!a.x) a.x = a.theta;
+  if (!a.y) a.y = a.theta;
+  if (!a.s) a.s = a.theta;
+  return launch_grouped_reduce(d, a, plan, c.skip, t, dg.chunks, dg.cbase, 0, (int64_t)t.chunks.size(), 0, c.dshared,
+                               c.dshared_ld, c.used, nullptr, nullptr, st);
+}
+
+// One device's share of the host call: the chunks [cs, ce) of the table and their instances.
+int grouped_reduce_shard(int dev, const mcpx_desc* d, const mcpx::SensArgs& a, const SensPlan& plan,
+                         const GroupReduceCall& c, const GroupTable& t, double* hpart, int64_t* hcount, int64_t cs,
+                         int64_t ce) {
+  HIP_TRY(hipSetDevice(dev));
+  int rc = check_device(dev);
+  if (rc) return rc;
+  const int n = d->n, m = d->m;
+  const int64_t ds = mcpx_theta_shared_dim(d->family, n, m), nsh = t.G * ds;
+  const int64_t b0 = t.chunks[(size_t)cs].first;
+  const int64_t nb = t.chunks[(size_t)ce - 1].first + t.chunks[(size_t)ce - 1].len - b0;
+  DevBuf<double> th, dx, dy, dsl, dgx, dgy, dgs, dout;
+  DevBuf<int32_t> dst, dmap;
+  DevBuf<uint8_t> dskip;
+  DevBuf<mcpx::GroupChunk> dch;
+  auto up = [&](DevBuf<double>& b, const double* h, size_t per) -> hipError_t {
+    if (!h || !per) return hipSuccess;
+    hipError_t e = b.alloc((size_t)nb * per);
+    return e != hipSuccess ? e : hipMemcpy(b.p, h + b0 * per, sizeof(double) * nb * per, hipMemcpyHostToDevice);
+  };
+  HIP_TRY(th.alloc((size_t)std::max<int64_t>(nsh, 1)));
+  if (nsh > 0) HIP_TRY(hipMemcpy(th.p, a.theta, sizeof(double) * (size_t)nsh, hipMemcpyHostToDevice));
+  HIP_TRY(up(dx, a.x, n)); HIP_TRY(up(dy, a.y, m)); HIP_TRY(up(dsl, a.s, m));
+  HIP_TRY(up(dgx, a.gx, n)); HIP_TRY(up(dgy, a.gy, m)); HIP_TRY(up(dgs, a.gs, m));
+  if (c.skip) {
+    HIP_TRY(dskip.alloc((size_t)nb));
+    HIP_TRY(hipMemcpy(dskip.p, c.skip + b0, (size_t)nb, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(dmap.alloc((size_t)nb));
+  HIP_TRY(hipMemcpy(dmap.p, t.map.data() + b0, sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice));
+  HIP_TRY(dch.alloc((size_t)(ce - cs)));
+  HIP_TRY(hipMemcpy(dch.p, t.chunks.data() + cs, sizeof(mcpx::GroupChunk) * (size_t)(ce - cs), hipMemcpyHostToDevice));
+  if (a.out) HIP_TRY(dout.alloc((size_t)nb * (n + m)));
+  if (a.status) HIP_TRY(dst.alloc((size_t)nb));
+  mcpx_desc dd = *d;
+  dd.batch = nb;
+  mcpx::SensArgs da = a;  // the same call on the shard's device buffers
+  da.theta = th.p;
+  da.x = dx.p ? dx.p : th.p;
+  da.y = dy.p ? dy.p : th.p;
+  da.s = dsl.p ? dsl.p : th.p;
+  da.gx = dgx.p;
+  da.gy = dgy.p;
+  da.gs = dgs.p;
+  da.out = dout.p;
+  da.status = dst.p;
+  da.group_map = dmap.p;
+  da.shared_ld = ds;
+  rc = launch_grouped_reduce(&dd, da, plan, dskip.p, t, dch.p, nullptr, cs, ce, b0, nullptr, 0, nullptr, hpart, hcount,
+                             nullptr);
+  if (rc) {
+    (void)hipDeviceSynchronize();  // nothing may still run on the buffers freed on return
+    return rc;
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  if (a.out) HIP_TRY(hipMemcpy(a.out + b0 * (n + m), dout.p, sizeof(double) * nb * (n + m), hipMemcpyDeviceToHost));
+  if (a.status) HIP_TRY(hipMemcpy(a.status + b0, dst.p, sizeof(int32_t) * nb, hipMemcpyDeviceToHost));
+  return MCPX_OK;
+}
+
+int grouped_reduce_host(const mcpx_desc* d, const GroupCall& g, mcpx::SensArgs a, const GroupReduceCall& c,
+                        int num_devices) {
+  SensPlan plan;
+  int rc;
+  if ((rc = grouped_reduce_checks(d, g, c, &a, &plan))) return rc;
+  const int64_t ds = mcpx_theta_shared_dim(d->family, d->n, d->m);
+  for (int32_t k = 0; k < g.G; ++k) {  // the empty sums
+    std::fill(c.dshared + k * c.dshared_ld, c.dshared + k * c.dshared_ld + ds, 0.0);
+    c.used[k] = 0;
+  }
+  if (d->batch == 0) return MCPX_OK;
+  if (mcpx_device_count() < 1) return fail(MCPX_ENODEV, "no HIP device visible");
+  GroupTable t;
+  build_groups(d, g.shared, g.shared_ld, g.G, g.off, ds, true, true, &t);
+  if (!t.packed.empty()) a.theta = t.packed.data();
+  const int64_t nch = (int64_t)t.chunks.size();
+  std::vector<double> hpart((size_t)(nch * ds));
+  std::vector<int64_t> hcount((size_t)nch, 0);
+  // shards are runs of whole chunks of the table: a shard may cut a group, never a chunk
+  rc = run_shards(num_devices, nch, [&](int dev, int64_t cs, int64_t ncs) {
+    return grouped_reduce_shard(dev, d, a, plan, c, t, hpart.data(), hcount.data(), cs, cs + ncs);
+  });
+  if (rc) return rc;
+  for (int32_t k = 0; k < g.G; ++k) {  // each group's chunk partials in its chunk order (grouped_reduce_fold)
+    double* out = c.dshared + k * c.dshared_ld;
+    for (int64_t q = t.cbase[(size_t)k]; q < t.cbase[(size_t)k + 1]; ++q) {
+      const double* p = hpart.data() + q * ds;
+      for (int64_t e = 0; e < ds; ++e) out[e] = out[e] + p[e];
+      c.used[k] += hcount[(size_t)q];
+    }
+  }
+  return MCPX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1404,6 +1760,93 @@ int mcpx_vjp_batch_shared_reduce(const mcpx_desc* d, const double* theta_shared,
   a.gy = gy;
   a.gs = gs;
   return shared_reduce_host(d, a, ReduceCall{skip, dshared, used}, num_devices);
+}
+
+int mcpx_solve_batch_grouped_device(const mcpx_desc* d, const double* theta_shared, int64_t shared_ld,
+                                    int32_t num_groups, const int64_t* group_offsets, const double* theta_var,
+                                    const double* x0, const double* y0, const double* s0, const mcpx_params* prm,
+                                    const mcpx_out* o, void* stream) {
+  mcpx::KernelArgs a;
+  SolvePlan plan;
+  bool empty = false;
+  const GroupCall g{theta_shared, shared_ld, num_groups, group_offsets};
+  int rc = prepare_grouped(d, g, theta_var, prm, o, &a, &plan, &empty);
+  if (rc || empty) return rc;
+  int dev = 0;
+  if ((rc = current_device(&dev))) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  GroupTable t;
+  build_groups(d, theta_shared, shared_ld, num_groups, group_offsets, 0, false, false, &t);
+  DevGroups dg;
+  HIP_TRY(dg.upload(t, st));
+  return launch_shared_chunks(d, theta_shared, theta_var, x0, y0, s0, o, a, plan, st, dg.map, shared_ld);
+}
+
+int mcpx_solve_batch_grouped(const mcpx_desc* d, const double* theta_shared, int64_t shared_ld, int32_t num_groups,
+                             const int64_t* group_offsets, const double* theta_var, const double* x0,
+                             const double* y0, const double* s0, const mcpx_params* prm, int num_devices,
+                             mcpx_out* o) {
+  mcpx::KernelArgs a;
+  SolvePlan plan;
+  bool empty = false;
+  const GroupCall g{theta_shared, shared_ld, num_groups, group_offsets};
+  const int rc = prepare_grouped(d, g, theta_var, prm, o, &a, &plan, &empty);
+  if (rc || empty) return rc;
+  GroupTable t;
+  build_groups(d, theta_shared, shared_ld, num_groups, group_offsets, mcpx_theta_shared_dim(d->family, d->n, d->m), true,
+               false, &t);
+  const double* blocks = t.packed.empty() ? theta_shared : t.packed.data();
+  return run_shards(num_devices, d->batch, [&](int dev, int64_t b0, int64_t nb) {
+    return solve_shard(dev, d, blocks, theta_var, x0, y0, s0, a, plan, o, b0, nb, &t);
+  });
+}
+
+int mcpx_vjp_batch_grouped_device(const mcpx_desc* d, const double* theta_shared, int64_t shared_ld,
+                                  int32_t num_groups, const int64_t* group_offsets, const double* x, const double* y,
+                                  const double* s, const double* gx, const double* gy, const double* gs,
+                                  double* dvar, int32_t* status, void* stream) {
+  mcpx::SensArgs a = sens_args(theta_shared, x, y, s, dvar, status);
+  a.gx = gx;
+  a.gy = gy;
+  a.gs = gs;
+  return grouped_vjp_device(d, GroupCall{theta_shared, shared_ld, num_groups, group_offsets}, a, stream);
+}
+
+int mcpx_vjp_batch_grouped(const mcpx_desc* d, const double* theta_shared, int64_t shared_ld, int32_t num_groups,
+                           const int64_t* group_offsets, const double* x, const double* y, const double* s,
+                           const double* gx, const double* gy, const double* gs, int num_devices, double* dvar,
+                           int32_t* status) {
+  mcpx::SensArgs a = sens_args(theta_shared, x, y, s, dvar, status);
+  a.gx = gx;
+  a.gy = gy;
+  a.gs = gs;
+  return grouped_vjp_host(d, GroupCall{theta_shared, shared_ld, num_groups, group_offsets}, a, num_devices);
+}
+
+int mcpx_vjp_batch_grouped_reduce_device(const mcpx_desc* d, const double* theta_shared, int64_t shared_ld,
+                                         int32_t num_groups, const int64_t* group_offsets, const double* x,
+                                         const double* y, const double* s, const double* gx, const double* gy,
+                                         const double* gs, const uint8_t* skip, double* dshared, int64_t dshared_ld,
+                                         int64_t* used, double* dvar, int32_t* status, void* stream) {
+  mcpx::SensArgs a = sens_args(theta_shared, x, y, s, dvar, status);
+  a.gx = gx;
+  a.gy = gy;
+  a.gs = gs;
+  return grouped_reduce_device(d, GroupCall{theta_shared, shared_ld, num_groups, group_offsets}, a,
+                               GroupReduceCall{skip, dshared, dshared_ld, used}, stream);
+}
+
+int mcpx_vjp_batch_grouped_reduce(const mcpx_desc* d, const double* theta_shared, int64_t shared_ld,
+                                  int32_t num_groups, const int64_t* group_offsets, const double* x, const double* y,
+                                  const double* s, const double* gx, const double* gy, const double* gs,
+                                  const uint8_t* skip, int num_devices, double* dshared, int64_t dshared_ld,
+                                  int64_t* used, double* dvar, int32_t* status) {
+  mcpx::SensArgs a = sens_args(theta_shared, x, y, s, dvar, status);
+  a.gx = gx;
+  a.gy = gy;
+  a.gs = gs;
+  return grouped_reduce_host(d, GroupCall{theta_shared, shared_ld, num_groups, group_offsets}, a,
+                             GroupReduceCall{skip, dshared, dshared_ld, used}, num_devices);
 }
 
 int mcpx_jvp_batch_shared_device(const mcpx_desc* d, const double* theta_shared, const double* x, const double* y,

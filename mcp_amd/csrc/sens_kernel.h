@@ -37,6 +37,10 @@ struct SensArgs {
   // same for every instance (theta_dot is then the per-instance block's, or NULL = +0.0).
   // Last, so that the kernels of generated modules built against this header are unaffected.
   const double* shared_dot;
+  // mcpx_vjp_batch_grouped* (the SPLIT pullback kernels; NULL otherwise): instance b's matrix block
+  // is theta + group_map[b]·shared_ld.
+  const int32_t* group_map;
+  int64_t shared_ld;
 };
 
 // Where a kernel's θ (and a JVP's θ̇) comes from.  kThetaFull: instance b's θ′ at
@@ -98,5 +102,30 @@ hipError_t launch_shared_reduce_partial(const ReduceArgs& a, int64_t nchunks, hi
 // dshared / used ← (first ? 0 : their value) + the partials / counts, chunks ascending.
 hipError_t launch_shared_reduce_fold(const double* part, const int64_t* count, int64_t nchunks, int64_t ds,
                                      bool first, double* dshared, int64_t* used, hipStream_t st);
+
+// The reduced gradient per group of a grouped batch (mcpx_vjp_batch_grouped_reduce*, grouped_reduce.hip).
+// A row of the chunk table: at most MCPX_REDUCE_CHUNK instances of one group, counted from the
+// group's first instance; the chunks ascend with the instances, empty groups own none.
+struct GroupChunk {
+  int64_t first;  // the chunk's first instance (index into the whole batch)
+  int32_t len;
+  int32_t group;
+};
+struct GroupReduceArgs {
+  ReduceArgs r;              // as above; the arrays' element 0 is instance inst0, r.chunk0 indexes `chunks`
+  const GroupChunk* chunks;  // the rows of the table (device) that the call covers: the batch's, or a shard's
+  int64_t inst0;
+};
+// dshared + g·dshared_ld [ds] ← +0.0 and used[g] ← 0 for g < G (the padding of dshared is not written).
+hipError_t launch_grouped_reduce_zero(double* dshared, int64_t dshared_ld, int64_t ds, int64_t G, int64_t* used,
+                                      hipStream_t st);
+// Partials of chunks [a.r.chunk0, a.r.chunk0 + nchunks) into a.r.part / a.r.count.
+hipError_t launch_grouped_reduce_partial(const GroupReduceArgs& a, int64_t nchunks, hipStream_t st);
+// The partials / counts of chunks [c0, c0 + nchunks) added, ascending, to dshared + g·dshared_ld and
+// used[g] of their groups g ∈ [g_lo, g_hi); cbase [G + 1] (device): group g owns the chunks
+// [cbase[g], cbase[g + 1]).  Continues each group's chain from what dshared[g] / used[g] hold.
+hipError_t launch_grouped_reduce_fold(const double* part, const int64_t* count, int64_t c0, int64_t nchunks,
+                                      const int64_t* cbase, int64_t g_lo, int64_t g_hi, int64_t ds, double* dshared,
+                                      int64_t dshared_ld, int64_t* used, hipStream_t st);
 
 }  // namespace mcpx

@@ -462,8 +462,10 @@ __global__ __launch_bounds__(64) void vjp_kernel(const SensArgs A) {
   const int64_t inst = blockIdx.x;
   const int n = A.n, m = A.m;
   const double* th_;
-  if constexpr (SPLIT) th_ = A.theta;
-  else th_ = A.theta + inst * A.theta_ld;
+  if constexpr (SPLIT) {
+    th_ = A.theta;
+    if (A.group_map) th_ += (int64_t)A.group_map[inst] * A.shared_ld;  // grouped batch: this instance's block
+  } else th_ = A.theta + inst * A.theta_ld;
   const double* th = th_;
   load_z(A, inst, ln, zs);
   __syncthreads();

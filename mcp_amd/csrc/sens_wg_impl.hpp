@@ -308,8 +308,11 @@ __device__ __forceinline__ void sens_instances(const WgSensArgs& W) {
     __syncthreads();
     if (inst >= W.batch) break;  // every workgroup reaches this exit
     const double* th_;
-    if constexpr (SPLIT) th_ = a.theta;
-    else th_ = a.theta + inst * a.theta_ld;
+    if constexpr (SPLIT) {
+      th_ = a.theta;
+      if constexpr (!JVP)  // grouped batch (mcpx_vjp_batch_grouped*): this instance's block
+        if (a.group_map) th_ += (int64_t)a.group_map[inst] * a.shared_ld;
+    } else th_ = a.theta + inst * a.theta_ld;
     const double* __restrict__ th = th_;
     const bool has_gs = a.gs || a.ga_s != 0.0;  // else ∂l/∂s = ZeroTangent
     auto gs_at = [&](int k) { return affine_ct(a.ga_s, zs[nr + k], a.gs ? a.gs + inst * m + k : nullptr); };
