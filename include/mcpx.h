@@ -38,7 +38,10 @@
  *
  * Conventions: all arrays are instance-major (instance b's data is contiguous,
  * stride `theta_ld` for θ); all buffers are caller-owned; the library keeps no
- * pointer after returning.  Return value 0 = OK, < 0 = API misuse / HIP error
+ * pointer after returning.  The theta_ld − p doubles after each instance's θ are
+ * never read or written by any call, the last instance's included: a θ buffer may
+ * end with its last instance, at (B − 1)·theta_ld + p doubles.  Return value
+ * 0 = OK, < 0 = API misuse / HIP error
  * (message via mcpx_last_error(), thread-local).  Numerical failure is never
  * an error: it is status[b] = MCPX_STATUS_FAILED, as in src/solver.jl:84-100,
  * 117-119, which never throws.

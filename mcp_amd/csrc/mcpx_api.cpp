@@ -310,6 +310,14 @@ hipError_t launch(int nmax, const mcpx::KernelArgs& a, int64_t nb, hipStream_t s
 // uint64 words of one instance's active-set mask: ⌈m/64⌉, at least 1 (include/mcpx.h)
 inline int64_t mask_words(int m) { return m > 64 ? (m + 63) / 64 : 1; }
 
+// Doubles a copy of `nb` strided instances may touch, `own` doubles each at stride `ld` >= own:
+// the last instance ends with its own doubles, not with the stride — the caller's buffer may
+// end there (include/mcpx.h: the ld − own doubles after an instance are never read).  Every
+// host-side copy of a strided θ block sizes itself here.
+inline size_t strided_span(int64_t nb, int64_t ld, int64_t own) {
+  return nb > 0 ? (size_t)((nb - 1) * ld + own) : 0;
+}
+
 // ---- grouped shared-matrix batches (mcpx_*_batch_grouped*) -------------------------------------
 
 // What a grouped call derives from its host metadata, once, before any launch.
@@ -663,8 +671,11 @@ int solve_shard(int dev, const mcpx_desc* d, const double* shared, const double*
   }
   const int64_t ds = shared ? mcpx_theta_shared_dim(d->family, n, m) : 0;
   const int64_t nsh = groups ? groups->G * ds : ds;  // doubles of the matrix block(s)
-  // the last instance of a chunk of the per-instance block: its own doubles, not the stride
-  const int64_t tail = shared ? mcpx_theta_var_dim(d->family, n, m) : ld;
+  // the last instance of a chunk: its own doubles, not the stride (strided_span) — the
+  // per-instance block of a shared-matrix batch, else the whole θ of the family or the module
+  const int64_t own = shared     ? mcpx_theta_var_dim(d->family, n, m)
+                      : plan.mod ? (int64_t)plan.mod->meta[kMetaP]
+                                 : mcpx_theta_dim(d->family, n, m);
   if (shared) HIP_TRY(sh.alloc((size_t)std::max<int64_t>(nsh, 1), cs));
   HIP_TRY(x.alloc((size_t)nb * n, cs)); HIP_TRY(y.alloc((size_t)nb * m, cs)); HIP_TRY(s.alloc((size_t)nb * m, cs));
   HIP_TRY(kkt.alloc(nb, cs)); HIP_TRY(eps.alloc(nb, cs)); HIP_TRY(outer.alloc(nb, cs));
@@ -686,7 +697,7 @@ int solve_shard(int dev, const mcpx_desc* d, const double* shared, const double*
     const int k = (int)(ci % nbuf);
     const int64_t cn = std::min(ch, nb - c0), g0 = b0 + c0;
     if (ci >= nbuf) HIP_TRY(hipStreamWaitEvent(us, P->consumed[k], 0));  // chunk ci - nbuf released buffer k
-    HIP_TRY(hipMemcpyAsync(th[k].p, theta + g0 * ld, sizeof(double) * (size_t)((cn - 1) * ld + tail),
+    HIP_TRY(hipMemcpyAsync(th[k].p, theta + g0 * ld, sizeof(double) * strided_span(cn, ld, own),
                            hipMemcpyHostToDevice, us));
     if (x0) HIP_TRY(hipMemcpyAsync(wx[k].p, x0 + g0 * n, sizeof(double) * cn * n, hipMemcpyHostToDevice, us));
     if (y0) HIP_TRY(hipMemcpyAsync(wy[k].p, y0 + g0 * m, sizeof(double) * cn * m, hipMemcpyHostToDevice, us));
@@ -945,8 +956,10 @@ int sens_shard(bool jvp, int dev, const mcpx_desc* d, const mcpx::SensArgs& a, c
       HIP_TRY(dsd.alloc(nsd));
       HIP_TRY(hipMemcpy(dsd.p, a.shared_dot, sizeof(double) * nsd, hipMemcpyHostToDevice));
     }
-  } else {
-    HIP_TRY(up(th, a.theta, (size_t)d->theta_ld));
+  } else if (nb) {  // θ at the caller's stride; the last instance's a.p doubles end the copy
+    HIP_TRY(th.alloc((size_t)nb * (size_t)d->theta_ld));
+    HIP_TRY(hipMemcpy(th.p, a.theta + b0 * d->theta_ld, sizeof(double) * strided_span(nb, d->theta_ld, a.p),
+                      hipMemcpyHostToDevice));
   }
   HIP_TRY(up(dx, a.x, n)); HIP_TRY(up(dy, a.y, m)); HIP_TRY(up(ds, a.s, m));
   HIP_TRY(up(dgx, a.gx, n)); HIP_TRY(up(dgy, a.gy, m)); HIP_TRY(up(dgs, a.gs, m));
